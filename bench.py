@@ -1,6 +1,6 @@
 """Benchmark of the assembly hot path: Melements/s assembled (global K + f).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the hot path over one mesh, from vertex coordinates + connectivity
@@ -18,7 +18,10 @@ ranges along the Morton curve of the centroids (BASELINE config 4).  Either way 
 shared between ranks are summed with one RCCL all-reduce of a packed interface buffer
 (pytorch_fem_solver_amd/parallel.py) on a side stream.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints
+it; --full adds the measurements beside the headline figure (stiffness-only launch in three
+cache states, public API per call, other sources, re-mesh set-up, P2 and Delaunay
+configurations, CPU baseline).  --dump-outputs DIR writes the last timed step's K and f.
 """
 
 from __future__ import annotations
@@ -75,7 +78,18 @@ def parse():
     p.add_argument("--delaunay-points", type=int, default=1_000_000,
                    help="vertices of the Delaunay meshes of other_configs (5000000 = the ~1e7-element "
                    "size of profiles/; generating it takes over a minute of host time)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the stiffness-only launch in "
+                   "three cache states, the committed profile's traffic, the public API per call, other "
+                   "sources, re-mesh set-up, other configurations (P2, Delaunay) and the CPU baseline "
+                   "(--no-other-configs / --no-cpu-baseline leave parts out)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/<name>.npy (float64; a fixed, seeded "
+                   "sample of the CSR values, at most 64 MB in all; f equal from run to run to rounding)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def algorithmic_bytes(n_elems, n_verts, nnz, with_load=True):
@@ -291,6 +305,46 @@ def event_ms(fn, reps, batches=5):
         torch.cuda.synchronize()
         out.append(a.elapsed_time(b) / reps)
     return float(np.median(out))
+
+
+#: --dump-outputs: CSR values kept (with their rows and columns), source entries kept whole, seed
+DUMP_K_SAMPLE = 500_000
+DUMP_F_WHOLE = 6_000_000
+DUMP_F_SAMPLE = 3_000_000
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, out, csr, suffix=""):
+    """The pair (CSR values of K, load vector f) the last timed step returned, as float64 .npy
+    files under `directory`: f whole (a seeded sample with its indices beyond DUMP_F_WHOLE entries)
+    and a seeded sample of DUMP_K_SAMPLE CSR values with their rows and columns in the engine's
+    CSR structure.  At most 60 MB in all; the same arguments give the same mesh and the same
+    sample, so that two builds can be compared output for output.  K is the same bit for bit
+    from run to run; f only to rounding (the launch sums source shares in LDS in arrival order;
+    TFEM_DETERMINISTIC=1 makes it bitwise, but that is another launch than the timed one)."""
+    vals, f = out
+    os.makedirs(directory, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(n, k):
+        return np.arange(n) if n <= k else np.sort(rng.choice(n, size=k, replace=False))
+
+    def save(name, arr):
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+    nnz = int(vals.numel())
+    pos = sample(nnz, DUMP_K_SAMPLE)
+    rowptr = csr[0].cpu().numpy()
+    save("K_values", vals.reshape(-1)[torch.from_numpy(pos).to(vals.device)].cpu().numpy())
+    save("K_rows", np.searchsorted(rowptr, pos, side="right") - 1)
+    save("K_cols", csr[1][torch.from_numpy(pos).to(csr[1].device)].cpu().numpy())
+    f = f.detach().reshape(-1)
+    if f.numel() <= DUMP_F_WHOLE:
+        save("f", f.cpu().numpy())
+    else:
+        idx = sample(f.numel(), DUMP_F_SAMPLE)
+        save("f", f[torch.from_numpy(idx).to(f.device)].cpu().numpy())
+        save("f_index", idx)
 
 
 def p2_config3():
@@ -558,44 +612,49 @@ def main():
         k_ms_probed = float(np.mean([starts[i].elapsed_time(ends[i]) for i in starts]))
     else:
         k_ms = k_ms_probed = elapsed * 1e3 / args.steps
+    if args.dump_outputs:
+        # before anything else runs on the engine: the last timed step's pair, complete after the syncs above
+        dump_outputs(args.dump_outputs, out, csr, "" if world == 1 else f"_rank{rank}")
 
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
         algo = algorithmic_bytes(n_elems, n_verts, nnz)
         algo_k = algorithmic_bytes(n_elems, n_verts, nnz, False)
         achieved = algo / (k_ms * 1e-3) / 1e9
-        profile = committed_profile(n, args.order, engine.kernel_name()) if world == 1 else {"fused": {}, "k_only": {}}
-        # the stiffness-only launch (the kernel BASELINE.json's 60 % target is quoted on): back to
-        # back (what a caller that re-assembles on a fixed mesh sees: its ~200 MB read set survives
-        # in the 256 MB memory-side cache) and cold (every launch behind 512 MB of unrelated writes)
-        k_vals = torch.empty(nnz)  # one output buffer, as in the step
-        for _ in range(30):
-            engine.bilinear(1.0, 0.0, out=k_vals)
-        torch.cuda.synchronize()
-        k_only_ms = event_ms(lambda: engine.bilinear(1.0, 0.0, out=k_vals), 50, batches=5)
-        scrub = torch.empty(64 * 1024 * 1024)  # 512 MB
-        cold = []
-        for _ in range(10):
-            scrub.fill_(1.0)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            engine.bilinear(1.0, 0.0, out=k_vals)
-            b.record()
+        profile = (committed_profile(n, args.order, engine.kernel_name()) if world == 1 and args.full
+                   else {"fused": {}, "k_only": {}})
+        if args.full:
+            # the stiffness-only launch (the kernel BASELINE.json's 60 % target is quoted on): back to
+            # back (what a caller that re-assembles on a fixed mesh sees: its ~200 MB read set survives
+            # in the 256 MB memory-side cache) and cold (every launch behind 512 MB of unrelated writes)
+            k_vals = torch.empty(nnz)  # one output buffer, as in the step
+            for _ in range(30):
+                engine.bilinear(1.0, 0.0, out=k_vals)
             torch.cuda.synchronize()
-            cold.append(a.elapsed_time(b))
-        # the same behind 512 MB of unrelated READS: the caches hold nothing of the launch's data
-        # either, but no dirty lines whose write-back (up to the 256 MB of the memory-side cache)
-        # shares the HBM with the launch
-        cold_read = []
-        for _ in range(10):
-            scrub.sum()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            engine.bilinear(1.0, 0.0, out=k_vals)
-            b.record()
-            torch.cuda.synchronize()
-            cold_read.append(a.elapsed_time(b))
-        del scrub
+            k_only_ms = event_ms(lambda: engine.bilinear(1.0, 0.0, out=k_vals), 50, batches=5)
+            scrub = torch.empty(64 * 1024 * 1024)  # 512 MB
+            cold = []
+            for _ in range(10):
+                scrub.fill_(1.0)
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                engine.bilinear(1.0, 0.0, out=k_vals)
+                b.record()
+                torch.cuda.synchronize()
+                cold.append(a.elapsed_time(b))
+            # the same behind 512 MB of unrelated READS: the caches hold nothing of the launch's data
+            # either, but no dirty lines whose write-back (up to the 256 MB of the memory-side cache)
+            # shares the HBM with the launch
+            cold_read = []
+            for _ in range(10):
+                scrub.sum()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                engine.bilinear(1.0, 0.0, out=k_vals)
+                b.record()
+                torch.cuda.synchronize()
+                cold_read.append(a.elapsed_time(b))
+            del scrub
         line = {
             "metric": "Melements/s assembled (global K + f)",
             "value": total_elems / (elapsed / args.steps) / 1e6,
@@ -652,36 +711,37 @@ def main():
                 "SURVEY.md 8(d)); the launch is bound by fp64 vector issue (76.9 M wave-instructions at 2.3-2.4 GHz), not by HBM: DESIGN.md sections 0 and 3"
                 + ("" if world == 1 else "; N > 1: kernel_ms = wall clock of the timed region / steps (two streams and a "
                    "collective per step), achieved = this rank's algorithmic bytes over it"),
-                "stiffness_only": {
-                    # the launch BASELINE.json's 60 % target is quoted on.  `frac` is the CACHE-FREE figure:
-                    # every launch behind 512 MB of unrelated reads, so that neither the L2s nor the 256 MB
-                    # memory-side cache (Infinity Cache) hold any of its ~200 MB read set.  Back to back into
-                    # one buffer (what a caller re-assembling on a fixed mesh sees) that read set survives
-                    # in the memory-side cache from launch to launch: `frac_back_to_back`; FETCH_SIZE
-                    # counts those hits as fetched bytes, so `traffic` is fabric traffic, not HBM traffic.
-                    # `frac_behind_writes`: every launch behind 512 MB of unrelated WRITES, whose
-                    # write-back (up to 256 MB of dirty lines) shares the HBM with the launch.
-                    "kernel_ms": float(np.median(cold_read)),
-                    "frac": algo_k / (float(np.median(cold_read)) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                    "achieved": algo_k / (float(np.median(cold_read)) * 1e-3) / 1e9,
-                    "state": "cold caches: behind 512 MB of unrelated reads",
-                    "back_to_back_ms": k_only_ms,
-                    "frac_back_to_back": algo_k / (k_only_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                    "behind_writes_ms": float(np.median(cold)),
-                    "frac_behind_writes": algo_k / (float(np.median(cold)) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                    "traffic": profile["k_only"].get("traffic"),
-                    "algorithmic_bytes_per_launch": algo_k,
-                },
             },
         }
-        for key, obj, ms in (("fused", line["roofline"], k_ms), ("k_only", line["roofline"]["stiffness_only"], k_only_ms)):  # traffic was counted back to back
-            for extra in ("kernel_ms_rocprofv3", "valu_utilisation"):
-                if extra in profile[key]:
-                    obj[extra] = profile[key][extra]
-            if obj["traffic"]:
-                obj["traffic_GBps"] = obj["traffic"] / (ms * 1e-3) / 1e9
-                obj["traffic_frac_of_peak"] = obj["traffic_GBps"] / HBM_PEAK_GBS
-        if world == 1:
+        if args.full:
+            line["roofline"]["stiffness_only"] = {
+                # the launch BASELINE.json's 60 % target is quoted on.  `frac` is the CACHE-FREE figure:
+                # every launch behind 512 MB of unrelated reads, so that neither the L2s nor the 256 MB
+                # memory-side cache (Infinity Cache) hold any of its ~200 MB read set.  Back to back into
+                # one buffer (what a caller re-assembling on a fixed mesh sees) that read set survives
+                # in the memory-side cache from launch to launch: `frac_back_to_back`; FETCH_SIZE
+                # counts those hits as fetched bytes, so `traffic` is fabric traffic, not HBM traffic.
+                # `frac_behind_writes`: every launch behind 512 MB of unrelated WRITES, whose
+                # write-back (up to 256 MB of dirty lines) shares the HBM with the launch.
+                "kernel_ms": float(np.median(cold_read)),
+                "frac": algo_k / (float(np.median(cold_read)) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "achieved": algo_k / (float(np.median(cold_read)) * 1e-3) / 1e9,
+                "state": "cold caches: behind 512 MB of unrelated reads",
+                "back_to_back_ms": k_only_ms,
+                "frac_back_to_back": algo_k / (k_only_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "behind_writes_ms": float(np.median(cold)),
+                "frac_behind_writes": algo_k / (float(np.median(cold)) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "traffic": profile["k_only"].get("traffic"),
+                "algorithmic_bytes_per_launch": algo_k,
+            }
+            for key, obj, ms in (("fused", line["roofline"], k_ms), ("k_only", line["roofline"]["stiffness_only"], k_only_ms)):  # traffic was counted back to back
+                for extra in ("kernel_ms_rocprofv3", "valu_utilisation"):
+                    if extra in profile[key]:
+                        obj[extra] = profile[key][extra]
+                if obj["traffic"]:
+                    obj["traffic_GBps"] = obj["traffic"] / (ms * 1e-3) / 1e9
+                    obj["traffic_frac_of_peak"] = obj["traffic_GBps"] / HBM_PEAK_GBS
+        if args.full and world == 1:
             line["roofline"]["profile_source"] = (
                 f"profiles/{PROFILE_TAG}_bench_pmc_summary.json (kernel sources {source_sha()})"
                 if profile["fused"] else "no committed profile of these kernel sources: traffic not quoted")
@@ -712,7 +772,7 @@ def main():
                 api_two_calls()
             torch.cuda.synchronize()
             line["api_two_calls_ms_per_step"] = (time.perf_counter() - t1) * 1e3 / 50
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             # the same launch with other sources: what the source itself costs (the launch is
             # bound by fp64 vector issue), and with pre-evaluated source values
             # streamed from HBM (round 1's step: the evaluation of f was outside the timed region)
@@ -739,7 +799,7 @@ def main():
             sources["tfem_source_eval alone (f at the integration points -> HBM)"] = {"kernel_ms": ms}
             del fq
             line["roofline"]["sources"] = sources
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             # what a caller who re-meshes pays per mesh: the same set-up on a second mesh of the
             # family (other jitter seed) in this process -- setup_ms above also holds what a
             # process pays once (torch loading its device kernels on first use, the library)
@@ -755,7 +815,7 @@ def main():
             del basis2, mesh2, other
             line["other_configs"] = {"C3_p2_stiffness_1e6": p2_config3()}
             line["other_configs"].update(delaunay_configs(args.delaunay_points, args.order))
-        if world == 1 and not args.no_cpu_baseline:  # rank 0 at N = 1 only
+        if args.full and world == 1 and not args.no_cpu_baseline:  # rank 0 at N = 1 only
             torch.set_default_device("cpu")
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.order)
         print(json.dumps(line), flush=True)

@@ -84,6 +84,48 @@ def test_bench_default_scaling_is_config_4_and_one_rank_over_rccl_takes_graphs(t
     assert args.scaling == "strong" and args.step_mode == "auto" and not args.interface_first
 
 
+def test_bench_plain_run_on_one_gpu_dumps_the_last_step(tmp_path):
+    """bench.py --gpus 1 without --full: the headline line alone (no CPU baseline, no other
+    configurations, no stiffness-only timings), exactly --steps timed steps, and --dump-outputs
+    holds what the last step computed -- K (seeded sample) and f against the numpy oracle."""
+    import numpy as np
+
+    sys.path.insert(0, REPO)
+    from conftest import scaled_error
+    from oracle import assembly_oracle as orc
+    from pytorch_fem_solver_amd import meshgen
+
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+           "--grid", "64", "--dump-outputs", str(out_dir)]
+    done = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert done.returncode == 0, done.stdout[-3000:] + done.stderr[-3000:]
+    lines = [line for line in done.stdout.splitlines() if line.startswith('{"metric"')]
+    assert len(lines) == 1, done.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["dtype"] == "f64" and out["higher_is_better"] is True and out["unit"] == "Melements/s"
+    for key in ("cpu_baseline", "other_configs", "api_ms_per_step"):
+        assert key not in out, key
+    assert "stiffness_only" not in out["roofline"]
+
+    mesh = meshgen.unit_square(64, 0.25, 0)
+    verts, tris = mesh["vertices"], mesh["triangles"]
+    nv = verts.shape[0]
+    rowptr, colind, slots = orc.csr_pattern(tris, nv)
+    k_local, _ = orc.p1_assemble(verts, tris, 3, "stiffness")
+    f_local, _ = orc.p1_assemble(verts, tris, 3, "load")
+    want_vals = orc.assemble_csr_values(k_local, slots, colind.shape[0])
+    want_f = orc.assemble_linear(f_local, tris, nv)
+    got = {name: np.load(out_dir / f"{name}.npy") for name in ("K_values", "K_rows", "K_cols", "f")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["K_values"].size == colind.shape[0]  # below the sample size: every entry, in CSR order
+    assert np.array_equal(got["K_rows"], np.repeat(np.arange(nv), np.diff(rowptr)))
+    assert np.array_equal(got["K_cols"], colind)
+    assert scaled_error(got["K_values"], want_vals) <= 1e-12
+    assert scaled_error(got["f"].reshape(want_f.shape), want_f) <= 1e-12
+
+
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_runs_with_two_ranks(scaling, tmp_path):
     """The driver's multi-GPU command line (bench.py under torch.distributed.run), two ranks on the

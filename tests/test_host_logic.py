@@ -877,6 +877,48 @@ def test_bench_reads_the_committed_profiles():
     assert bench.committed_profile(100, 3, "k_p1_rings") == {"fused": {}, "k_only": {}}  # another workload
 
 
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py: a plain run by default (--full off), --steps taken as given (at least 1), and
+    --dump-outputs writes the last step's pair -- a seeded sample of the CSR values with their rows
+    and columns, f whole -- as float64, the same files from the same inputs, within 64 MB."""
+    import bench
+
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "3", "--full", "--dump-outputs", str(tmp_path)])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == str(tmp_path)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+    counts = np.arange(300_000) % 5 + 1  # row i holds i % 5 + 1 entries: more than the sample keeps
+    rowptr = np.concatenate([[0], np.cumsum(counts)])
+    nnz = int(rowptr[-1])
+    assert nnz > bench.DUMP_K_SAMPLE
+    colind = (np.arange(nnz) % 1000).astype(np.int32)
+    vals = torch.arange(nnz, dtype=torch.float64) * 0.5
+    f = torch.linspace(0.0, 1.0, 300_000, dtype=torch.float64)
+    csr = (torch.from_numpy(rowptr), torch.from_numpy(colind))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), (vals, f), csr)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["K_cols.npy", "K_rows.npy", "K_values.npy", "f.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / name) for name in names) <= 64 * 2**20
+    got = {}
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+        got[name[:-4]] = a
+    pos = (got["K_values"] * 2.0).astype(np.int64)  # value k / 2 sits at CSR position k
+    assert pos.size == bench.DUMP_K_SAMPLE and np.all(np.diff(pos) > 0)
+    rows = got["K_rows"].astype(np.int64)
+    assert np.all(rowptr[rows] <= pos) and np.all(pos < rowptr[rows + 1])
+    assert np.array_equal(got["K_cols"], colind[pos])
+    assert np.array_equal(got["f"], f.numpy())
+
+
 def test_host_builders_do_not_depend_on_the_thread_count_and_keep_their_digest():
     """The once-per-mesh builders (CSR pattern, slot map, ring plan) are multi-threaded
     (csrc/tfem_threads.hpp): 1, 3 and the default number of threads give identical bytes, and the

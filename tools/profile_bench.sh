@@ -6,7 +6,7 @@ set -e
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_r03
 mkdir -p $OUT
-CMD="python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-other-configs"
+CMD="python3 bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-other-configs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- $CMD > $OUT/bench_under_rocprof.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc1 -o run -- $CMD > $OUT/pmc1.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pmc2 -o run -- $CMD > $OUT/pmc2.log 2>&1
