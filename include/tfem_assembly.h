@@ -351,6 +351,14 @@ int tfem_p1_assemble_rings(const void *coords, int real_bytes, int64_t n_verts, 
                            double alpha, double beta, const void *plan_device,
                            const int64_t *plan_layout_host, void *vals, int64_t nnz,
                            const void *fq, int64_t n_elems, void *fout, void *stream);
+/* y[n_verts] = (alpha * stiffness + beta * mass) u over the same ring plan, without the CSR values
+ * (abstract_basis.py:74-93 with basis.py:64-85: the operator the reference assembles, applied
+ * instead of stored).  Every entry of y is written once (0 for a vertex without elements); u and y
+ * (DEVICE, n_verts reals each, the plan's vertex numbering) must not overlap.  u == NULL: y =
+ * diag(K).  Plans with long rows (layout[23] > 0) are served by a second launch for those rows. */
+int tfem_p1_apply_rings(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
+                        double alpha, double beta, const void *plan_device,
+                        const int64_t *plan_layout_host, const void *u, void *y, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Source programs: the coefficient f of the linear form f(x_q) * v

@@ -16,7 +16,7 @@ from .basis import (
 )
 from .element import AbstractElement, ElementLine, ElementTri
 from .mesh import AbstractMesh, FracturesTri, MeshData, MeshesTri, MeshTri
-from .sparse import CSRMatrix
+from .sparse import CSRMatrix, FormOperator
 
 __all__ = [
     "Basis",
@@ -29,5 +29,6 @@ __all__ = [
     "MeshTri",
     "MeshesTri",
     "CSRMatrix",
+    "FormOperator",
     "meshgen",
 ]

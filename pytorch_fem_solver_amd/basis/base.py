@@ -17,7 +17,7 @@ import warnings
 import torch
 
 from .. import _native
-from ..sparse import CSRMatrix
+from ..sparse import CSRMatrix, FormOperator
 from . import forms
 
 #: above this many bytes the dense (N, N) layout of the reference is not materialised
@@ -180,10 +180,20 @@ class AbstractBasis(abc.ABC):
     def integrate_bilinear_form(self, function, *args, layout=None, **kwargs):
         """Global operator of a bilinear form (abstract_basis.py:74-93).
 
-        ``layout``: "dense" (the reference's (N, N) tensor), "csr" (``CSRMatrix``) or None
-        = dense while it fits ``DENSE_LIMIT_BYTES``, CSR beyond.
+        ``layout``: "dense" (the reference's (N, N) tensor), "csr" (``CSRMatrix``), "operator"
+        (``FormOperator``: to apply and solve with; matrix-free for ``alpha * v_grad @ v_grad.mT +
+        beta * v @ v.mT`` on a P1 basis with a ring plan, the assembled CSR otherwise) or None =
+        dense while it fits ``DENSE_LIMIT_BYTES``, CSR beyond.
         """
         expr = forms.trace(function, self, args, kwargs)
+        if layout == "operator" and isinstance(expr, forms.BilinearExpr) and self._engine.may_apply_matrix_free():
+            # nothing is launched here: the ring plan is built on first use, and a basis whose fans
+            # turn out to have no ring form assembles the CSR operator then
+            engine, alpha, beta = self._engine, expr.alpha, expr.beta
+            return FormOperator(
+                engine.n_dofs, engine.dtype, engine.home,
+                lambda: engine.wrap_csr_home(engine.bilinear(alpha, beta)), engine=engine, alpha=alpha, beta=beta,
+            )
         if isinstance(expr, forms.BilinearExpr):
             vals = self._engine.bilinear(expr.alpha, expr.beta)
         else:
@@ -242,6 +252,8 @@ class AbstractBasis(abc.ABC):
         return program
 
     def _finish_matrix(self, vals, layout):
+        if layout == "operator":  # any form the matrix-free launch does not cover: the assembled CSR
+            return FormOperator.from_csr(self._engine.wrap_csr_home(vals))
         matrix = self._engine.wrap_csr(vals)
         n = matrix.shape[0]
         if layout is None:
@@ -331,8 +343,10 @@ class AbstractBasis(abc.ABC):
         """Dense solve on the interior DoFs (abstract_basis.py:177-195).  A CSRMatrix beyond
         DENSE_SOLVE_LIMIT rows (or method="cg") is solved by Jacobi-preconditioned conjugate
         gradients on the CSR values (CSRMatrix.solve_cg; symmetric positive definite forms):
-        the step after the assembly for operators the reference cannot hold."""
-        if isinstance(matrix, CSRMatrix) and (method == "cg" or (method is None and matrix.shape[0] > self.DENSE_SOLVE_LIMIT)):
+        the step after the assembly for operators the reference cannot hold.
+        A FormOperator (layout="operator") is always solved by CG, matrix-free where it is."""
+        if isinstance(matrix, FormOperator) or (
+                isinstance(matrix, CSRMatrix) and (method == "cg" or (method is None and matrix.shape[0] > self.DENSE_SOLVE_LIMIT))):
             free = self._basis_parameters["inner_dofs"] if only_inner_dofs is True else None
             x, _, _ = matrix.solve_cg(vector, free=free)
             if free is None:

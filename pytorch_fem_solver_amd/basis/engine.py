@@ -1075,6 +1075,52 @@ class AssemblyEngine:
             return fout
         return (vals, fout) if with_load else vals
 
+    # ------------------------------------------------------------------ matrix-free operator
+    def may_apply_matrix_free(self):
+        """Whether a ring plan CAN exist for this basis (P1 on one mesh, the ring kernel not
+        switched away) -- known without building it; ring_plan() decides on first use."""
+        return self.kernel in ("auto", "rings") and self._p1_plan_eligible()
+
+    def _apply_rings(self, alpha, beta, u, out=None):
+        """One tfem_p1_apply_rings launch in the ENGINE's numbering: (alpha * stiffness + beta *
+        mass) u without the CSR values, u None: the diagonal.  Launches over the ring plan
+        whenever it exists, whatever _use_rings() prefers for the assembly."""
+        rings = self.ring_plan()
+        if rings is None:
+            raise NotImplementedError("the matrix-free operator needs the ring plan (P1, fans with a ring form)")
+        d = self._inputs()
+        if u is not None:
+            u = u.to(self.device, self.dtype).reshape(-1).contiguous()
+            if u.shape[0] != self.n_dofs:
+                raise ValueError(f"apply: u has {u.shape[0]} entries, the operator {self.n_dofs} columns")
+        y = self._output(out, self.n_dofs, "operator result")
+        if u is not None and y.data_ptr() == u.data_ptr():
+            raise ValueError("apply: out must not be u")
+        with torch.cuda.device(self.device):
+            _native.check(
+                self.lib.tfem_p1_apply_rings(
+                    _native.ptr(d["coords"]), self.real_bytes, self.n_dofs, self.quad_order, float(alpha),
+                    float(beta), _native.ptr(rings["blob"]), c_void_p(rings["layout"].ctypes.data),
+                    _native.ptr(u), _native.ptr(y), self._stream(),
+                )
+            )
+        return y
+
+    def apply(self, alpha, beta, u, out=None):
+        """(alpha * stiffness + beta * mass) u, matrix-free over the ring plan; u and the result
+        (flat, n_dofs) in the caller's numbering.  ``out``: a preallocated device buffer."""
+        if self._perm is None:
+            return self._apply_rings(alpha, beta, u, out)
+        y = self._dofs_out(self._apply_rings(alpha, beta, self._dofs_in(u.to(self.device).reshape(-1))))
+        if out is not None:
+            return self._output(out, self.n_dofs, "operator result").copy_(y)
+        return y
+
+    def operator_diagonal(self, alpha, beta):
+        """diag(alpha * stiffness + beta * mass) in the caller's numbering (Jacobi preconditioner),
+        from the same launch without u."""
+        return self._dofs_out(self._apply_rings(alpha, beta, None))
+
     def prepared_system(self, alpha, beta, out, fq=None, source=None, tiles=None):
         """The launch of assemble_system(alpha, beta, fq | source, out=out, tiles=tiles) with every
         argument converted ONCE: the returned callable only enqueues on the current stream

@@ -1,0 +1,335 @@
+// Matrix-free P1 operator over a ring plan: y = (alpha * stiffness + beta * mass) u without the
+// CSR values (abstract_basis.py:74-93 with basis.py:64-85, applied instead of stored).
+//
+// The row form of k_p1_rings (tfem_rings.hip) already builds every row of K in registers: one
+// lane owns one vertex v, ring_row evaluates its fan from tile-local coordinates in LDS and hands
+// back the diagonal and the off-diagonal entries in fan order.  Here the tile also stages u of its
+// local vertices (owned rows and halo) beside the coordinates, and the lane forms
+//     y_v = K_vv u_v + sum_i K_{v, n_i} u_{n_i}
+// and writes that one number: no CSR stage, no permutation, no row offsets.  With chunked plans a
+// wave's rows are 64 consecutive vertices, so the stores of y coalesce.  u == NULL writes diag(K)
+// (Jacobi preconditioner).
+//
+// Tile walk: as the matrix-only launches of k_p1_rings (one contiguous range of the tile list
+// per XCD, workgroups strided inside it); per tile one LDS stage and two barriers.  The vertex
+// ids of the next tile are fetched while the current tile's rows are evaluated.
+//
+// Plans with long rows (TFEM_RING_LONG=1: vertices with 8 .. 15 neighbours listed apart): the
+// tile launch skips those rows and k_p1_apply_long_rows forms them, sixteen lanes per row as in
+// k_p1_long_rows.
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+
+#include "tfem_rings_kernel.hpp"
+
+namespace tfem {
+
+template <typename T>
+struct ApplyArgs {
+  const T *u;  // NULL: y = diag(K)
+  T *y;
+  unsigned u_bytes, y_bytes;
+};
+
+template <typename T, int SLOTS, bool MASS, bool CHUNK, bool DIAG>
+__global__ __launch_bounds__(kRingBlock) void k_p1_apply_rows(const RingArgs<T> a, const ApplyArgs<T> b) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ring_smem[];
+  T *xy = reinterpret_cast<T *>(ring_smem);  // [2 * lds_vert]
+  T *us = xy + 2 * a.lds_vert;               // [lds_vert]
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int per = (a.n_tiles + 7) / 8;
+  const int xcd = blockIdx.x & 7;
+  const int stride = gridDim.x >> 3;
+  const ring_rsrc_t r_coords = ring_rsrc(a.coords, a.coords_bytes);
+  const ring_rsrc_t r_plan = ring_rsrc(a.plan, a.plan_bytes);
+  const ring_rsrc_t r_u = ring_rsrc(b.u, b.u_bytes);
+  const ring_rsrc_t r_y = ring_rsrc(b.y, b.y_bytes);
+  constexpr unsigned kRecBytes = unsigned(4 * RingRec<SLOTS>::kWords);
+  constexpr unsigned kNone = 0x3FFFFFFu;  // index behind every array: buffer loads give 0
+
+  auto tile_at = [&](int j) { return (j < per && xcd * per + j < a.n_tiles) ? xcd * per + j : -1; };
+  // vertex ids of a tile: the lane's own row and halo vertex number tid (as k_p1_rings)
+  auto load_ids = [&](const RingDesc &d, unsigned &g_own, unsigned &g_halo) {
+    const int r = d.row0 + lane;
+    if (CHUNK)
+      g_own = unsigned(d.gid0 + lane);
+    else
+      g_own = __builtin_amdgcn_raw_buffer_load_b32(
+          r_plan, a.off_gid + (r < d.row1 ? unsigned(d.vert_off + r) : kNone) * 4u, 0, 0);
+    const int h = d.n_own + tid;
+    g_halo = __builtin_amdgcn_raw_buffer_load_b32(
+        r_plan, a.off_gid + (h < d.n_vert ? unsigned(d.vert_off + h) : kNone) * 4u, 0, 0);
+  };
+  auto load_u = [&](unsigned g) {
+    if constexpr (sizeof(T) == 8) {
+      const ru32x2 v{__builtin_amdgcn_raw_buffer_load_b32(r_u, g * 8u, 0, 0),
+                     __builtin_amdgcn_raw_buffer_load_b32(r_u, g * 8u + 4u, 0, 0)};
+      return __builtin_bit_cast(double, v);
+    } else {
+      return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_u, g * 4u, 0, 0));
+    }
+  };
+
+  int j = int(blockIdx.x >> 3);
+  int t = tile_at(j);
+  if (t < 0) return;  // whole workgroup, before any barrier
+  RingDesc d = ring_desc<CHUNK>(a.plan, a.off_desc, t, wave);
+  unsigned gid_own, gid_halo;
+  load_ids(d, gid_own, gid_halo);
+  for (;;) {
+    const int r = d.row0 + lane;
+    const bool own = r < d.row1;
+    const int h = d.n_own + tid;
+    const bool halo = h < d.n_vert;
+    // coordinates and u of this tile's vertices, the row record
+    T own_x, own_y, halo_x, halo_y, own_u = T(0), halo_u = T(0);
+    ring_load_xy<T>(r_coords, own ? gid_own : kNone, own_x, own_y);
+    ring_load_xy<T>(r_coords, halo ? gid_halo : kNone, halo_x, halo_y);
+    if (!DIAG) {
+      own_u = load_u(own ? gid_own : kNone);
+      halo_u = load_u(halo ? gid_halo : kNone);
+    }
+    RingRec<SLOTS> rec;
+    ring_load_rec<SLOTS>(r_plan, a.off_rows + (own ? unsigned(d.row_off + r) : kNone) * kRecBytes, rec);
+    // vertex ids of the next tile, behind this tile's loads
+    const unsigned gid_row = gid_own;
+    const int t_n = tile_at(j + stride);
+    RingDesc dn = d;
+    if (t_n >= 0) {
+      dn = ring_desc<CHUNK>(a.plan, a.off_desc, t_n, wave);
+      load_ids(dn, gid_own, gid_halo);
+    }
+    if (own) {
+      xy[2 * r] = own_x;
+      xy[2 * r + 1] = own_y;
+      if (!DIAG) us[r] = own_u;
+    }
+    if (halo) {
+      xy[2 * h] = halo_x;
+      xy[2 * h + 1] = halo_y;
+      if (!DIAG) us[h] = halo_u;
+    }
+    __syncthreads();
+    T off[SLOTS + 1], diag, sdets[SLOTS];
+    const uint32_t lv = unsigned(own ? r : 0);
+    ring_row<T, SLOTS, MASS, false>(a, rec, lv, xy, off, diag, sdets);
+    const int k = rec.k();
+    T yv = diag;
+    if (!DIAG) {
+      yv = diag * us[lv];
+#pragma unroll
+      for (int i = 0; i < SLOTS; ++i) {
+        // off[i] for i >= k is scratch of ring_row: those slots take no part
+        const T ui = us[i < k ? rec.id(i) : lv];
+        yv = yv + (i < k ? off[i] : T(0)) * ui;
+      }
+    }
+    // a long row (k = 0, bit 31 of the last record word) is written by k_p1_apply_long_rows
+    const bool is_long = SLOTS == 7 && k == 0 && (rec.w[3] >> 31) != 0u;
+    if (own && !is_long) {
+      if constexpr (sizeof(T) == 8)
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ru32x2, yv), r_y, gid_row * 8u, 0, 0);
+      else
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, yv), r_y, gid_row * 4u, 0, 0);
+    }
+    if (t_n < 0) break;
+    __syncthreads();  // every row has read the stage before the next tile overwrites it
+    j += stride;
+    t = t_n;
+    d = dn;
+  }
+}
+
+// Rows of vertices with 8 .. 15 neighbours (plans with long rows): sixteen lanes per row, lane i =
+// slot i of the fan, global ids; the entries are formed as in k_p1_long_rows and multiplied by u
+// of their columns, the products summed over the sixteen lanes.
+template <typename T, bool MASS, bool DIAG>
+__global__ __launch_bounds__(kRingBlock) void k_p1_apply_long_rows(const T *coords, const unsigned char *plan,
+                                                                   unsigned off_long, int n_long, const T *u, T *y,
+                                                                   T stiff_w, T mass_d, T mass_o) {
+  const int gtid = int(blockIdx.x) * kRingBlock + int(threadIdx.x);
+  const int row = gtid >> 4, i = gtid & 15;
+  const bool live = row < n_long;
+  const uint32_t *rec = reinterpret_cast<const uint32_t *>(plan + off_long) + 24 * size_t(live ? row : 0);
+  const uint32_t v = rec[0];
+  const int k = int(rec[2] & 0xFFu);
+  const bool slot = live && i < k;
+  const uint32_t flag = slot ? (rec[3] >> (2 * i)) & 3u : 0u;
+  const int nxt = i + 1 == k ? 0 : i + 1;
+  const uint32_t g0 = rec[4 + (slot ? i : 0)], g1 = rec[4 + (slot ? nxt : 0)];
+  const T xv = coords[2 * size_t(v)], yv = coords[2 * size_t(v) + 1];
+  const T ecx = coords[2 * size_t(g0)] - xv, ecy = coords[2 * size_t(g0) + 1] - yv;
+  const T enx = coords[2 * size_t(g1)] - xv, eny = coords[2 * size_t(g1) + 1] - yv;
+  const T qc = ecx * ecx + ecy * ecy, qn = enx * enx + eny * eny;
+  const T p = ecx * enx + ecy * eny;
+  const T cross = ecx * eny - ecy * enx;
+  const T cs = flag_weight<T>(stiff_w, flag) * fast_rcp<T>(flag ? cross : T(1));
+  T here = cs * (p - qn), next = cs * (p - qc);  // to column n_i, to column n_next
+  T sdet = T(0);
+  if (MASS) {
+    sdet = flag_weight<T>(T(1), flag) * cross;
+    here = here + mass_o * sdet;
+    next = next + mass_o * sdet;
+  }
+  const int lane = int(threadIdx.x) & 63;
+  const int from = (lane & ~15) + (i == 0 ? (k > 0 ? k - 1 : 0) : i - 1);
+  const T entry = here + __shfl(next, from, 64);
+  T sum = here + next, dsum = sdet;
+  T prod = (!DIAG && slot) ? entry * u[g0] : T(0);
+#pragma unroll
+  for (int m = 8; m >= 1; m >>= 1) {
+    sum = sum + __shfl_xor(sum, m, 64);
+    if (MASS) dsum = dsum + __shfl_xor(dsum, m, 64);
+    if (!DIAG) prod = prod + __shfl_xor(prod, m, 64);
+  }
+  if (!live || i != 0) return;
+  // stiffness rows sum to zero; the mass part is taken out of the sum and added on the diagonal
+  const T diag = MASS ? mass_d * dsum - (sum - T(2) * mass_o * dsum) : -sum;
+  y[v] = DIAG ? diag : diag * u[v] + prod;
+}
+
+template <typename T, int SLOTS, bool CHUNK>
+static void *pick_apply_diag(bool mass, bool diag) {
+  if (mass)
+    return diag ? reinterpret_cast<void *>(k_p1_apply_rows<T, SLOTS, true, CHUNK, true>)
+                : reinterpret_cast<void *>(k_p1_apply_rows<T, SLOTS, true, CHUNK, false>);
+  return diag ? reinterpret_cast<void *>(k_p1_apply_rows<T, SLOTS, false, CHUNK, true>)
+              : reinterpret_cast<void *>(k_p1_apply_rows<T, SLOTS, false, CHUNK, false>);
+}
+
+template <typename T>
+static void *pick_apply_kernel(int slots, bool chunk, bool mass, bool diag) {
+  if (slots == 7)
+    return chunk ? pick_apply_diag<T, 7, true>(mass, diag) : pick_apply_diag<T, 7, false>(mass, diag);
+  return chunk ? pick_apply_diag<T, 15, true>(mass, diag) : pick_apply_diag<T, 15, false>(mass, diag);
+}
+
+static int apply_cu_count() {
+  static int cached = 0;
+  if (cached == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+      cached = prop.multiProcessorCount;
+    else
+      cached = 256;
+  }
+  return cached;
+}
+
+template <typename T>
+static int launch_apply(const void *coords, int64_t n_verts, int quad_order, double alpha, double beta,
+                        const unsigned char *plan, const int64_t *z, const void *u, void *y, hipStream_t stream) {
+  TriTables tables;
+  if (!build_tri_tables(quad_order, int(sizeof(T)), &tables))
+    return fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
+  if (z[0] == 0) return TFEM_OK;
+  if (!coords || !plan || !y) return fail(TFEM_ERR_INVALID_ARGUMENT, "NULL pointer");
+  // the capacities the matrix launches check (tfem_rings.hip: launch_rings)
+  if (z[0] < 0 || z[4] > kRingBlock || z[3] > kRingVertCap || z[4] > z[3] || z[14] > kRingHaloCap ||
+      !((z[6] == 7 && z[7] == 4) || (z[6] == 15 && z[7] == 8)) || (z[5] > z[6] + 1 && z[23] == 0) || z[5] > 16)
+    return fail(TFEM_ERR_INVALID_ARGUMENT, "ring plan exceeds the kernel's capacities");
+  const int64_t rb = int64_t(sizeof(T));
+  const int64_t extents[3] = {n_verts * 2 * rb, z[12], n_verts * rb};
+  for (int64_t e : extents)
+    if (e < 0 || e >= (int64_t(1) << 32))
+      return fail(TFEM_ERR_INDEX_RANGE, "an array of %lld bytes does not fit the 32-bit offsets "
+                  "of the ring kernel", (long long)e);
+  RingArgs<T> a;
+  std::memset(&a, 0, sizeof(a));
+  a.coords = static_cast<const T *>(coords);
+  a.plan = plan;
+  a.coords_bytes = unsigned(extents[0]);
+  a.plan_bytes = unsigned(extents[1]);
+  a.off_desc = unsigned(z[8]);
+  a.off_rows = unsigned(z[9]);
+  a.off_rowstart = unsigned(z[10]);
+  a.off_gid = unsigned(z[11]);
+  a.n_tiles = int(z[0]);
+  a.lds_vert = (int(z[3]) + 1) & ~1;
+  // W = sum_q w_q/2 and M_ij = sum_q (w_q/2) l_i l_j in T, in quadrature order: the same numbers
+  // the matrix launches use (tfem_rings.hip)
+  T w = T(0), md = T(0), mo = T(0);
+  for (int q = 0; q < tables.nq; ++q) {
+    w = w + T(tables.hw[q]);
+    md = md + T(tables.hw[q]) * (T(tables.lam[q][0]) * T(tables.lam[q][0]));
+    mo = mo + T(tables.hw[q]) * (T(tables.lam[q][0]) * T(tables.lam[q][1]));
+  }
+  a.stiff_w = T(alpha) * w;
+  a.mass_d = T(beta) * md;
+  a.mass_o = T(beta) * mo;
+  ApplyArgs<T> b;
+  b.u = static_cast<const T *>(u);
+  b.y = static_cast<T *>(y);
+  b.u_bytes = u ? unsigned(extents[2]) : 0u;
+  b.y_bytes = unsigned(extents[2]);
+  const bool mass = beta != 0.0, diag = u == nullptr, chunk = z[13] != 0;
+  const int slots = int(z[6]);
+  void *kernel = pick_apply_kernel<T>(slots, chunk, mass, diag);
+  const size_t lds = size_t(3 * a.lds_vert) * sizeof(T);
+  // resident workgroups per CU, once per (kernel, LDS size): the launch path does no runtime query
+  struct Occupancy { void *kernel; size_t lds; int per_cu; };
+  static Occupancy occ_cache[32];
+  static int occ_used = 0;
+  static std::mutex occ_mutex;
+  int per_cu = 0;
+  {
+    std::lock_guard<std::mutex> guard(occ_mutex);
+    for (int i = 0; i < occ_used; ++i)
+      if (occ_cache[i].kernel == kernel && occ_cache[i].lds == lds) per_cu = occ_cache[i].per_cu;
+    if (per_cu == 0) {
+      hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kRingBlock, lds);
+      if (oe != hipSuccess || per_cu < 1) per_cu = 1;
+      if (occ_used < 32) occ_cache[occ_used++] = {kernel, lds, per_cu};
+    }
+  }
+  const int per = int((z[0] + 7) / 8);
+  const int blocks = std::min(per * 8, (apply_cu_count() * per_cu / 8) * 8);
+  void *params[] = {&a, &b};
+  hipError_t e = hipLaunchKernel(kernel, dim3(unsigned(std::max(blocks, 8))), dim3(kRingBlock), params, lds, stream);
+  if (e != hipSuccess) return fail(TFEM_ERR_HIP, "apply kernel launch: %s", hipGetErrorString(e));
+  if (z[23] > 0) {  // the rows of the vertices with 8 .. 15 neighbours
+    const dim3 lgrid{unsigned((16 * z[23] + kRingBlock - 1) / kRingBlock)};
+    const T *uu = static_cast<const T *>(u);
+    T *yy = static_cast<T *>(y);
+    const unsigned off_long = unsigned(z[22]);
+    const int n_long = int(z[23]);
+    if (mass && diag)
+      hipLaunchKernelGGL((k_p1_apply_long_rows<T, true, true>), lgrid, dim3(kRingBlock), 0, stream, a.coords, plan,
+                         off_long, n_long, uu, yy, a.stiff_w, a.mass_d, a.mass_o);
+    else if (mass)
+      hipLaunchKernelGGL((k_p1_apply_long_rows<T, true, false>), lgrid, dim3(kRingBlock), 0, stream, a.coords, plan,
+                         off_long, n_long, uu, yy, a.stiff_w, a.mass_d, a.mass_o);
+    else if (diag)
+      hipLaunchKernelGGL((k_p1_apply_long_rows<T, false, true>), lgrid, dim3(kRingBlock), 0, stream, a.coords, plan,
+                         off_long, n_long, uu, yy, a.stiff_w, a.mass_d, a.mass_o);
+    else
+      hipLaunchKernelGGL((k_p1_apply_long_rows<T, false, false>), lgrid, dim3(kRingBlock), 0, stream, a.coords, plan,
+                         off_long, n_long, uu, yy, a.stiff_w, a.mass_d, a.mass_o);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(TFEM_ERR_HIP, "long-row apply launch: %s", hipGetErrorString(e));
+  }
+  return TFEM_OK;
+}
+
+}  // namespace tfem
+
+extern "C" {
+
+int tfem_p1_apply_rings(const void *coords, int real_bytes, int64_t n_verts, int quad_order, double alpha,
+                        double beta, const void *plan_device, const int64_t *plan_layout_host, const void *u,
+                        void *y, void *stream) {
+  using namespace tfem;
+  if (real_bytes != 4 && real_bytes != 8) return fail(TFEM_ERR_INVALID_ARGUMENT, "real_bytes must be 4 or 8");
+  if (!plan_layout_host) return fail(TFEM_ERR_INVALID_ARGUMENT, "plan_layout_host is NULL");
+  if (n_verts < 0) return fail(TFEM_ERR_INVALID_ARGUMENT, "negative size");
+  const unsigned char *plan = static_cast<const unsigned char *>(plan_device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return real_bytes == 8 ? launch_apply<double>(coords, n_verts, quad_order, alpha, beta, plan, plan_layout_host, u, y, s)
+                         : launch_apply<float>(coords, n_verts, quad_order, alpha, beta, plan, plan_layout_host, u, y, s);
+}
+
+}  // extern "C"

@@ -153,38 +153,167 @@ class CSRMatrix:
             free_s = None if free is None else inv[free.to(self.device).reshape(-1)]
             x, it, res = self._stored().solve_cg(to_stored(b), free_s, to_stored(x0), rtol, maxiter)
             return x[inv].reshape(b.shape), it, res
-        n = self.shape[0]
-        shape = b.shape
-        b = b.to(self.device, self.dtype).reshape(-1)
-        mask = torch.ones(n, dtype=self.dtype, device=self.device)
-        if free is not None:
-            mask.zero_()
-            mask[free.to(self.device).reshape(-1)] = 1
-        x = torch.zeros(n, dtype=self.dtype, device=self.device) if x0 is None else x0.to(self.device, self.dtype).reshape(-1).clone()
-        inv_diag = mask / torch.where(self.diagonal() != 0, self.diagonal(), torch.ones_like(mask))
-        r = mask * (b - self.matvec(x))
-        x = x.clone()
-        z = inv_diag * r
-        p = z.clone()
-        rz = torch.dot(r, z)
-        b_norm = torch.linalg.vector_norm(mask * b).clamp_min(torch.finfo(self.dtype).tiny)
-        maxiter = maxiter or 10 * n
-        it, res = 0, float(torch.linalg.vector_norm(r) / b_norm)
-        while it < maxiter and res > rtol:
-            ap = mask * self.matvec(p)
-            alpha = rz / torch.dot(p, ap)
-            x += alpha * p
-            r -= alpha * ap
-            z = inv_diag * r
-            rz_new = torch.dot(r, z)
-            p = z + (rz_new / rz) * p
-            rz = rz_new
-            it += 1
-            if it % 25 == 0 or it == maxiter:  # one host synchronisation every 25 iterations
-                res = float(torch.linalg.vector_norm(r) / b_norm)
-        res = float(torch.linalg.vector_norm(r) / b_norm)
-        return x.reshape(shape), it, res
+        x, it, res = conjugate_gradients(self.matvec, self.diagonal(), b, free, x0, rtol, maxiter)
+        return x.reshape(b.shape), it, res
 
     def __repr__(self):
         extra = "" if self.perm is None else ", stored in a renumbering of the DoFs"
         return f"CSRMatrix(shape={self.shape}, nnz={self.nnz}, dtype={self.dtype}, device={self.device}{extra})"
+
+
+def conjugate_gradients(matvec, diagonal, b, free=None, x0=None, rtol=1e-12, maxiter=None):
+    """Jacobi-preconditioned conjugate gradients for a symmetric positive definite operator given
+    by ``matvec`` (flat (N,) -> (N,)) and its ``diagonal`` ((N,) tensor), restricted to the DoFs
+    ``free`` (index tensor; the others keep x0's values, 0 by default).  Vectors live on the
+    diagonal's device and dtype.  Returns (x (N,), iterations, relative residual).  The loop of
+    ``CSRMatrix.solve_cg`` and ``FormOperator.solve_cg``."""
+    n = diagonal.shape[0]
+    dtype, device = diagonal.dtype, diagonal.device
+    b = b.to(device, dtype).reshape(-1)
+    mask = torch.ones(n, dtype=dtype, device=device)
+    if free is not None:
+        mask.zero_()
+        mask[free.to(device).reshape(-1)] = 1
+    x = torch.zeros(n, dtype=dtype, device=device) if x0 is None else x0.to(device, dtype).reshape(-1).clone()
+    inv_diag = mask / torch.where(diagonal != 0, diagonal, torch.ones_like(mask))
+    r = mask * (b - matvec(x))
+    x = x.clone()
+    z = inv_diag * r
+    p = z.clone()
+    rz = torch.dot(r, z)
+    b_norm = torch.linalg.vector_norm(mask * b).clamp_min(torch.finfo(dtype).tiny)
+    maxiter = maxiter or 10 * n
+    it, res = 0, float(torch.linalg.vector_norm(r) / b_norm)
+    while it < maxiter and res > rtol:
+        ap = mask * matvec(p)
+        alpha = rz / torch.dot(p, ap)
+        x += alpha * p
+        r -= alpha * ap
+        z = inv_diag * r
+        rz_new = torch.dot(r, z)
+        p = z + (rz_new / rz) * p
+        rz = rz_new
+        it += 1
+        if it % 25 == 0 or it == maxiter:  # one host synchronisation every 25 iterations
+            res = float(torch.linalg.vector_norm(r) / b_norm)
+    res = float(torch.linalg.vector_norm(r) / b_norm)
+    return x, it, res
+
+
+class _OperatorApply(torch.autograd.Function):
+    """u -> K u of a symmetric operator, differentiable in u: the backward is the same
+    application (K^T = K), e.g. for energy-norm losses u^T K u."""
+
+    @staticmethod
+    def forward(ctx, u, op):
+        ctx.op = op
+        return op._apply(u.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        return ctx.op._apply(grad_out), None
+
+
+class FormOperator:
+    """The global operator of a bilinear form, to apply and to solve with, without necessarily
+    storing it (``Basis.integrate_bilinear_form(..., layout="operator")``).
+
+    Matrix-free (``matrix_free`` True): ``alpha * stiffness + beta * mass`` of a P1 basis whose
+    engine has a ring plan; every ``matvec`` is one tfem_p1_apply_rings launch that forms the rows
+    of K in registers and writes K u -- the values of K are never stored.  Otherwise the operator
+    wraps the CSRMatrix of today's assembly and applies it with tfem_csr_spmv (P2, fractures, any
+    other integrand, meshes without a ring plan); the interface and the results are the same.
+    Vectors are taken and returned in the caller's DoF numbering, of shape (N,) or (N, 1)."""
+
+    def __init__(self, n, dtype, device, assemble, engine=None, alpha=0.0, beta=0.0, symmetric=True):
+        self.shape = (int(n), int(n))
+        self.dtype = dtype
+        self.device = device
+        self._assemble = assemble  # () -> CSRMatrix on `device`: the assembled form
+        self._engine = engine      # None: the CSR path only
+        self.alpha, self.beta = float(alpha), float(beta)
+        self._symmetric = symmetric
+        self._csr = None
+        self._matrix_free = None if engine is not None else False
+
+    @classmethod
+    def from_csr(cls, csr, symmetric=False):
+        return cls(csr.shape[0], csr.dtype, csr.device, lambda: csr, symmetric=symmetric)
+
+    @property
+    def matrix_free(self):
+        """Decided on first use: the ring plan is built then (as for an assembly), not before."""
+        if self._matrix_free is None:
+            try:
+                self._matrix_free = self._engine.ring_plan() is not None
+            except NotImplementedError:
+                self._matrix_free = False
+        return self._matrix_free
+
+    def to_csr(self):
+        """The assembled operator (CSRMatrix) through the existing assembly path (cached)."""
+        if self._csr is None:
+            self._csr = self._assemble()
+        return self._csr
+
+    def _check(self, x):
+        flat = x.reshape(-1)
+        if flat.shape[0] != self.shape[1]:
+            raise ValueError(f"matvec: x has {flat.shape[0]} entries, the operator {self.shape[1]} columns")
+        return flat
+
+    def _apply(self, x):
+        flat = self._check(x)
+        if self.matrix_free:
+            engine = self._engine
+            y = engine._home(engine.apply(self.alpha, self.beta, flat))
+        else:
+            y = self.to_csr().matvec(flat.to(self.device))
+        return y.reshape(x.shape)
+
+    def matvec(self, x):
+        """K x for x of shape (N,) or (N, 1); differentiable in x for symmetric forms."""
+        if x.requires_grad and torch.is_grad_enabled():
+            if not self._symmetric:
+                raise NotImplementedError("matvec: the gradient needs the transpose of a non-symmetric form")
+            return _OperatorApply.apply(x, self)
+        return self._apply(x)
+
+    def __matmul__(self, x):
+        return self.matvec(x)
+
+    def diagonal(self):
+        """diag(K), shape (N,)."""
+        if self.matrix_free:
+            engine = self._engine
+            return engine._home(engine.operator_diagonal(self.alpha, self.beta))
+        return self.to_csr().diagonal()
+
+    def solve_cg(self, b, free=None, x0=None, rtol=1e-12, maxiter=None):
+        """Jacobi-preconditioned CG on the DoFs ``free``: the contract and the results of
+        ``CSRMatrix.solve_cg``.  Matrix-free, every iteration is one apply launch, and the loop
+        runs in the engine's numbering (vectors translated once at the boundary)."""
+        if not self.matrix_free:
+            return self.to_csr().solve_cg(b, free, x0, rtol, maxiter)
+        engine = self._engine
+        dev, dtype = engine.device, engine.dtype
+        inv = None if engine._inv is None else engine._inv.to(dev)
+
+        def inward(v):
+            return None if v is None else engine._dofs_in(v.to(dev, dtype).reshape(-1))
+
+        free_e = None
+        if free is not None:
+            free_e = free.to(dev).reshape(-1)
+            if inv is not None:
+                free_e = inv[free_e]
+        x, it, res = conjugate_gradients(
+            lambda p: engine._apply_rings(self.alpha, self.beta, p), engine._apply_rings(self.alpha, self.beta, None),
+            inward(b), free_e, inward(x0), rtol, maxiter,
+        )
+        return engine._home(engine._dofs_out(x)).reshape(b.shape), it, res
+
+    def __repr__(self):
+        kind = "matrix-free" if self._matrix_free else ("CSR" if self._matrix_free is False else "unresolved")
+        return f"FormOperator(shape={self.shape}, dtype={self.dtype}, device={self.device}, {kind})"
