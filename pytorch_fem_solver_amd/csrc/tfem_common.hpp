@@ -1,7 +1,9 @@
-// Shared host-side helpers of libtfem_hip: error reporting and the reference-element tables.
+// Shared host-side helpers of libtfem_hip: error reporting, launch sizing and the reference-element
+// tables.
 #pragma once
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 
@@ -10,6 +12,19 @@
 namespace tfem {
 
 int fail(int status, const char *fmt, ...);
+
+// Launch helpers of the kernels (tfem_host.cpp; not exported from the library).  CUs of the
+// current device, 256 if the query fails; asked once.
+#pragma GCC visibility push(hidden)
+int device_cu_count();
+// Resident workgroups of `block` lanes per CU for `kernel` with `lds` bytes of dynamic LDS, 1 if
+// the query fails or answers < 1.  The answer (and the one-off attribute for more than 64 KB of
+// LDS) is kept per (kernel, LDS size): the launch path of a prepared step does no runtime query.
+int resident_per_cu(const void *kernel, int block, size_t lds, int *per_cu);
+// TFEM_ERR_INDEX_RANGE unless each of the n array sizes in `bytes` lies in [0, limit): the kernel
+// named `kernel` addresses them with 32-bit offsets.
+int check_extents(const char *kernel, const int64_t *bytes, int n, int64_t limit = int64_t(1) << 32);
+#pragma GCC visibility pop
 
 constexpr int kMaxQuad = 6;
 

@@ -1,5 +1,7 @@
-// Host side of libtfem_hip: status/error plumbing, reference-element tables and the
-// symbolic (CSR pattern + slot map) phase.  No device code in this file.
+// Host side of libtfem_hip: status/error plumbing, launch sizing, reference-element tables and
+// the symbolic (CSR pattern + slot map) phase.  No device code in this file.
+#include <hip/hip_runtime.h>
+
 #include <algorithm>
 #include <cstring>
 #include <numeric>
@@ -7,6 +9,7 @@
 
 #include <chrono>
 #include <memory>
+#include <mutex>
 #include <cstdio>
 #include <cstdlib>
 
@@ -23,6 +26,49 @@ int fail(int status, const char *fmt, ...) {
   vsnprintf(g_last_error, sizeof(g_last_error), fmt, ap);
   va_end(ap);
   return status;
+}
+
+int device_cu_count() {
+  static const int cached = [] {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+      return prop.multiProcessorCount;
+    return 256;
+  }();
+  return cached;
+}
+
+int resident_per_cu(const void *kernel, int block, size_t lds, int *per_cu) {
+  struct Occupancy { const void *kernel; size_t lds; int per_cu; };
+  constexpr int kCache = 64;
+  static Occupancy cache[kCache];
+  static int used = 0;
+  static std::mutex mutex;
+  std::lock_guard<std::mutex> guard(mutex);
+  for (int i = 0; i < used; ++i)
+    if (cache[i].kernel == kernel && cache[i].lds == lds) {
+      *per_cu = cache[i].per_cu;
+      return TFEM_OK;
+    }
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return fail(TFEM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+  }
+  int n = 0;
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, lds);
+  if (e != hipSuccess || n < 1) n = 1;
+  if (used < kCache) cache[used++] = {kernel, lds, n};
+  *per_cu = n;
+  return TFEM_OK;
+}
+
+int check_extents(const char *kernel, const int64_t *bytes, int n, int64_t limit) {
+  for (int i = 0; i < n; ++i)
+    if (bytes[i] < 0 || bytes[i] >= limit)
+      return fail(TFEM_ERR_INDEX_RANGE, "an array of %lld bytes does not fit the 32-bit offsets of the %s",
+                  (long long)bytes[i], kernel);
+  return TFEM_OK;
 }
 
 // Literals of the reference, element_tri.py:77-130 (15-digit truncations included).

@@ -314,10 +314,8 @@ static int launch_p2_load(const void *coords, int quad_order, const unsigned cha
     return fail(TFEM_ERR_INVALID_ARGUMENT, "P2 row plan exceeds the kernel's capacities");
   const int64_t rb = int64_t(sizeof(T));
   const int64_t extents[4] = {z[2] * 2 * rb, z[16], n_elems * tables.nq * rb, n_dofs * rb};
-  for (int64_t e : extents)
-    if (e < 0 || e >= int64_t(kP2LoadPast))
-      return fail(TFEM_ERR_INDEX_RANGE, "an array of %lld bytes does not fit the 32-bit offsets "
-                  "of the P2 load-vector kernel", (long long)e);
+  const int st = check_extents("P2 load-vector kernel", extents, 4, int64_t(kP2LoadPast));
+  if (st != TFEM_OK) return st;
   P2LoadArgs<T> a;
   std::memset(&a, 0, sizeof(a));
   a.coords = static_cast<const T *>(coords);

@@ -26,7 +26,6 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 
 #include "tfem_common.hpp"
 #include "tfem_rowkit.hpp"
@@ -721,10 +720,8 @@ static int launch_p2_rows(const void *coords, int quad_order, double alpha, doub
     return fail(TFEM_ERR_INVALID_ARGUMENT, "P2 row plan exceeds the kernel's capacities");
   const int64_t rb = int64_t(sizeof(T));
   const int64_t extents[3] = {z[2] * 2 * rb, z[16], nnz * rb};
-  for (int64_t e : extents)
-    if (e < 0 || e >= (int64_t(1) << 32))
-      return fail(TFEM_ERR_INDEX_RANGE, "an array of %lld bytes does not fit the 32-bit offsets "
-                  "of the P2 row kernel", (long long)e);
+  int st = check_extents("P2 row kernel", extents, 3);
+  if (st != TFEM_OK) return st;
   const bool mass = beta != 0.0;
   // row 0 (vertex DoF at p0) / row 3 (edge DoF (p0, p1)) of the constant maps, in T, sums in
   // quadrature order like the reference's (integrand * dx).sum(-3)
@@ -777,38 +774,13 @@ static int launch_p2_rows(const void *coords, int quad_order, double alpha, doub
       return fail(TFEM_ERR_INVALID_ARGUMENT, "P2 row plan exceeds the kernel's capacities");
     const size_t lds = size_t(4 * a.lds_vert) * sizeof(T) + size_t(kP2Waves) * size_t(kP2StageHalf) * sizeof(T);
     void *kernel = mass ? reinterpret_cast<void *>(k_p2_rows_all<T, true>) : reinterpret_cast<void *>(k_p2_rows_all<T, false>);
-    static std::mutex occ_mutex;
-    static struct { void *kernel; size_t lds; int per_cu; } occ[8];
-    static int occ_used = 0;
     int per_cu = 0;
-    {
-      std::lock_guard<std::mutex> guard(occ_mutex);
-      for (int i = 0; i < occ_used; ++i)
-        if (occ[i].kernel == kernel && occ[i].lds == lds) per_cu = occ[i].per_cu;
-      if (per_cu == 0) {
-        if (lds > 64 * 1024) {
-          hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-          if (e != hipSuccess) return fail(TFEM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
-        hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kP2Block, lds);
-        if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-        if (occ_used < 8) {
-          occ[occ_used].kernel = kernel;
-          occ[occ_used].lds = lds;
-          occ[occ_used++].per_cu = per_cu;
-        }
-      }
-    }
+    st = resident_per_cu(kernel, kP2Block, lds, &per_cu);
+    if (st != TFEM_OK) return st;
     if (const char *v = std::getenv("TFEM_P2_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(v)));
-    int cus = 256, dev = 0;
-    hipDeviceProp_t prop;
-    static int cu_count = 0;
-    if (cu_count == 0 && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cu_count = prop.multiProcessorCount;
-    if (cu_count > 0) cus = cu_count;
     const int64_t n_all = z[0] + z[1];
     const int per = int((n_all + 31) / 32) * 4;
-    const int blocks = std::min(per * 8, (cus * per_cu / 8) * 8);
+    const int blocks = std::min(per * 8, (device_cu_count() * per_cu / 8) * 8);
     const dim3 grid{unsigned(blocks)}, block{unsigned(kP2Block)};
     void *params[] = {&a};
     hipError_t e = hipLaunchKernel(kernel, grid, block, params, lds, stream);

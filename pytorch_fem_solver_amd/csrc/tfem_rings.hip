@@ -21,61 +21,24 @@
 // 24 bytes of connectivity the row's triangles take.
 #include <cmath>
 #include <cstdio>
-#include <mutex>
 #include <vector>
 
 #include "tfem_rings_kernel.hpp"
 
 namespace tfem {
 
-// Rows of vertices with 8 .. 15 neighbours in a plan with long rows (tfem_rings_host.cpp):
-// SIXTEEN lanes per row, lane i = slot i of the fan, coordinates by global ids.  A lane
-// evaluates its slot's triangle (ring_row's formulas), takes what the previous slot's triangle
-// adds to its own column from the lane before it (slot 0 from slot k - 1), and writes its entry;
-// the diagonal follows from the sum over the sixteen lanes.
+// Rows of vertices with 8 .. 15 neighbours in a plan with long rows: sixteen lanes per row
+// (ring_long_slot); each slot lane writes its entry, lane 0 the diagonal.
 template <typename T, bool MASS>
 __global__ __launch_bounds__(kRingBlock) void k_p1_long_rows(const T *coords, const unsigned char *plan,
                                                              unsigned off_long, int n_long, T *vals, T stiff_w,
                                                              T mass_d, T mass_o) {
-  const int gtid = int(blockIdx.x) * kRingBlock + int(threadIdx.x);
-  const int row = gtid >> 4, i = gtid & 15;
-  const bool live = row < n_long;
-  const uint32_t *rec = reinterpret_cast<const uint32_t *>(plan + off_long) + 24 * size_t(live ? row : 0);
-  const uint32_t v = rec[0];
-  const int k = int(rec[2] & 0xFFu);
-  const int dpos = int(rec[2] >> 8);
-  const bool slot = live && i < k;
-  const uint32_t flag = slot ? (rec[3] >> (2 * i)) & 3u : 0u;
-  const int nxt = i + 1 == k ? 0 : i + 1;
-  const uint32_t g0 = rec[4 + (slot ? i : 0)], g1 = rec[4 + (slot ? nxt : 0)];
-  const T xv = coords[2 * size_t(v)], yv = coords[2 * size_t(v) + 1];
-  const T ecx = coords[2 * size_t(g0)] - xv, ecy = coords[2 * size_t(g0) + 1] - yv;
-  const T enx = coords[2 * size_t(g1)] - xv, eny = coords[2 * size_t(g1) + 1] - yv;
-  const T qc = ecx * ecx + ecy * ecy, qn = enx * enx + eny * eny;
-  const T p = ecx * enx + ecy * eny;
-  const T cross = ecx * eny - ecy * enx;
-  const T cs = flag_weight<T>(stiff_w, flag) * fast_rcp<T>(flag ? cross : T(1));
-  T here = cs * (p - qn), next = cs * (p - qc);  // to column n_i, to column n_next
-  T sdet = T(0);
-  if (MASS) {
-    sdet = flag_weight<T>(T(1), flag) * cross;
-    here = here + mass_o * sdet;
-    next = next + mass_o * sdet;
-  }
-  const int lane = int(threadIdx.x) & 63;
-  const int from = (lane & ~15) + (i == 0 ? (k > 0 ? k - 1 : 0) : i - 1);
-  const T entry = here + __shfl(next, from, 64);
-  T sum = here + next, dsum = sdet;
-#pragma unroll
-  for (int m = 8; m >= 1; m >>= 1) {
-    sum = sum + __shfl_xor(sum, m, 64);
-    if (MASS) dsum = dsum + __shfl_xor(dsum, m, 64);
-  }
-  if (!slot) return;
-  T *out = vals + rec[1];
-  out[int((rec[19 + i / 8] >> (4 * (i % 8))) & 15u)] = entry;
-  // stiffness rows sum to zero; the mass part is taken out of the sum and added on the diagonal
-  if (i == 0) out[dpos] = MASS ? mass_d * dsum - (sum - T(2) * mass_o * dsum) : -sum;
+  RingLongSlot<T> s;
+  ring_long_slot<T, MASS, false>(coords, plan, off_long, n_long, stiff_w, mass_o, nullptr, s);
+  if (!s.slot) return;
+  T *out = vals + s.rec[1];
+  out[int((s.rec[19 + s.i / 8] >> (4 * (s.i % 8))) & 15u)] = s.entry;
+  if (s.i == 0) out[s.dpos] = ring_diag<T, MASS>(s.sum, s.dsum, mass_d, mass_o);
 }
 
 struct RingLaunch {
@@ -96,19 +59,6 @@ struct RingLaunch {
   int flags = 0;          // > 0: ablation build (wrong results by design)
   unsigned long long *stamps = nullptr;
 };
-
-static int ring_cu_count() {
-  static int cached = 0;
-  if (cached == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cached = prop.multiProcessorCount;
-    else
-      cached = 256;
-  }
-  return cached;
-}
 
 // load vector alone (vals == NULL): the matrix part of the row is dead code
 template <typename T, int SLOTS, bool CHUNK>
@@ -163,28 +113,20 @@ static int launch_rings(const RingLaunch &L) {
   if (src && L.fq) return fail(TFEM_ERR_INVALID_ARGUMENT, "source values AND a source program");
   if (!kmat && !load) return fail(TFEM_ERR_INVALID_ARGUMENT, "nothing to assemble");
   if (!L.coords || !L.plan || (load && !L.fout)) return fail(TFEM_ERR_INVALID_ARGUMENT, "NULL pointer");
-  if (z[0] < 0 || z[4] > kRingBlock || z[3] > kRingVertCap || z[4] > z[3] || z[14] > kRingHaloCap ||
-      !((z[6] == 7 && z[7] == 4) || (z[6] == 15 && z[7] == 8)) || (z[5] > z[6] + 1 && z[23] == 0) || z[5] > 16)
-    return fail(TFEM_ERR_INVALID_ARGUMENT, "ring plan exceeds the kernel's capacities");
   RingArgs<T> a;
-  std::memset(&a, 0, sizeof(a));
-  a.coords = static_cast<const T *>(L.coords);
-  a.plan = L.plan;
-  a.vals = static_cast<T *>(L.vals);
+  int st = ring_args_init<T>(tables, z, L.coords, L.plan, L.n_verts, L.alpha, L.beta, a);
+  if (st != TFEM_OK) return st;
   const int64_t rb = int64_t(sizeof(T));
-  const int64_t extents[5] = {L.n_verts * 2 * rb, z[12], kmat ? L.nnz * rb : 0,
-                              (load && !src) ? L.n_elems * tables.nq * rb : 0, load ? L.n_verts * rb : 0};
-  for (int64_t e : extents)
-    if (e < 0 || e >= (int64_t(1) << 32))
-      return fail(TFEM_ERR_INDEX_RANGE, "an array of %lld bytes does not fit the 32-bit offsets "
-                  "of the ring kernel", (long long)e);
-  a.coords_bytes = unsigned(extents[0]);
-  a.plan_bytes = unsigned(extents[1]);
-  a.vals_bytes = unsigned(extents[2]);
+  const int64_t extents[3] = {kmat ? L.nnz * rb : 0, (load && !src) ? L.n_elems * tables.nq * rb : 0,
+                              load ? L.n_verts * rb : 0};
+  st = check_extents("ring kernel", extents, 3);
+  if (st != TFEM_OK) return st;
+  a.vals = static_cast<T *>(L.vals);
   a.fq = static_cast<const T *>(L.fq);
   a.fout = static_cast<T *>(L.fout);
-  a.fq_bytes = unsigned(extents[3]);
-  a.fout_bytes = unsigned(extents[4]);
+  a.vals_bytes = unsigned(extents[0]);
+  a.fq_bytes = unsigned(extents[1]);
+  a.fout_bytes = unsigned(extents[2]);
   a.off_elems = unsigned(z[15]);
   a.off_telems = unsigned(z[16]);
   // measured at 1e7 elements: the matrix-only launch is 4-6 % faster with one contiguous range
@@ -238,13 +180,9 @@ static int launch_rings(const RingLaunch &L) {
     a.chain_len = int(z[25]);
     if (a.chain_len < 1 || z[24] == 0 || z[26] == 0)
       return fail(TFEM_ERR_INVALID_ARGUMENT, "the ring plan carries no chain order (layout of an older build?)");
-    const int st = src_convert<T>(L.source, &a.src);
+    st = src_convert<T>(L.source, &a.src);
     if (st != TFEM_OK) return st;
   }
-  a.off_desc = unsigned(z[8]);
-  a.off_rows = unsigned(z[9]);
-  a.off_rowstart = unsigned(z[10]);
-  a.off_gid = unsigned(z[11]);
   const int64_t t_first = L.tile_first, t_count = L.tile_count < 0 ? z[0] - L.tile_first : L.tile_count;
   if (t_first < 0 || t_count < 0 || t_first + t_count > z[0])
     return fail(TFEM_ERR_INVALID_ARGUMENT, "tile range [%lld, +%lld) outside the plan's %lld tiles",
@@ -269,19 +207,6 @@ static int launch_rings(const RingLaunch &L) {
   } else {
     a.off_desc += 80u * unsigned(t_first);
   }
-  a.lds_vert = (int(z[3]) + 1) & ~1;
-  // W = sum_q w_q/2 and M_ij = sum_q (w_q/2) l_i l_j, formed in T in quadrature order.  The
-  // rules of element_tri.py:77-130 are symmetric, so M has one diagonal and one off-diagonal
-  // value (up to rounding: entries 00 and 01 are used).
-  T w = T(0), md = T(0), mo = T(0);
-  for (int q = 0; q < tables.nq; ++q) {
-    w = w + T(tables.hw[q]);
-    md = md + T(tables.hw[q]) * (T(tables.lam[q][0]) * T(tables.lam[q][0]));
-    mo = mo + T(tables.hw[q]) * (T(tables.lam[q][0]) * T(tables.lam[q][1]));
-  }
-  a.stiff_w = T(L.alpha) * w;
-  a.mass_d = T(L.beta) * md;
-  a.mass_o = T(L.beta) * mo;
   const bool mass = L.beta != 0.0;
   const int slots = int(z[6]);
   a.lds_elem = load ? int(z[17]) : 0;
@@ -318,28 +243,10 @@ static int launch_rings(const RingLaunch &L) {
                        : reinterpret_cast<void *>(k_p1_rings<T, 7, false, false, 0, true>);
     }
   }
-  // resident workgroups: what LDS and registers allow per CU, on every CU.  The answer (and the
-  // one-off attribute for more than 64 KB of LDS) is kept per (kernel, LDS size): the launch path
-  // of a prepared step does no runtime query
-  struct Occupancy { void *kernel; size_t lds; int per_cu; };
-  static Occupancy occ_cache[16];
-  static int occ_used = 0;
-  static std::mutex occ_mutex;
+  // resident workgroups: what LDS and registers allow per CU, on every CU
   int per_cu = 0;
-  {
-    std::lock_guard<std::mutex> guard(occ_mutex);
-    for (int i = 0; i < occ_used; ++i)
-      if (occ_cache[i].kernel == kernel && occ_cache[i].lds == lds) per_cu = occ_cache[i].per_cu;
-    if (per_cu == 0) {
-      if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return fail(TFEM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-      }
-      hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kRingBlock, lds);
-      if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-      if (occ_used < 16) occ_cache[occ_used++] = {kernel, lds, per_cu};
-    }
-  }
+  st = resident_per_cu(kernel, kRingBlock, lds, &per_cu);
+  if (st != TFEM_OK) return st;
   const int deal = a.xcd_interleave > 0 ? a.xcd_interleave : 1;
   int per = int((t_count + 8 * deal - 1) / (8 * deal)) * deal;
   if (src) {  // blocks of the chain order, dealt to the XCDs round-robin: workgroups per XCD that get one
@@ -351,7 +258,7 @@ static int launch_rings(const RingLaunch &L) {
   // TFEM_RINGS_RESERVE_CUS: CUs per XCD this launch leaves free (a sharded step: the kernels of
   // the interface exchange of the previous step -- pack, RCCL's all-reduce, unpack -- find room
   // beside the persistent workgroups of this one)
-  int cus = ring_cu_count();
+  int cus = device_cu_count();
   if (const char *v = std::getenv("TFEM_RINGS_RESERVE_CUS")) cus = std::max(8, cus - 8 * std::max(0, std::atoi(v)));
   const int blocks = std::min(per * 8, (cus * per_cu / 8) * 8);
   const dim3 grid{unsigned(blocks)}, block{unsigned(kRingBlock)};
@@ -424,6 +331,28 @@ static int launch_rings(const RingLaunch &L) {
   return TFEM_OK;
 }
 
+// The exported launches (tfem_p1_assemble_rings*): argument checks, the launch description and
+// the developer switch TFEM_RINGS_PER_CU (tools/time_rings.py).  flags > 0: ablation build.
+static int ring_entry(const void *coords, int real_bytes, int64_t n_verts, int quad_order, double alpha,
+                      double beta, const void *plan_device, const int64_t *plan_layout_host, void *vals,
+                      int64_t nnz, const void *fq, const tfem_source_program *source, int64_t n_elems,
+                      void *fout, int64_t tile_first, int64_t tile_count, int flags, void *stream) {
+  if (real_bytes != 4 && real_bytes != 8)
+    return fail(TFEM_ERR_INVALID_ARGUMENT, "real_bytes must be 4 or 8");
+  if (!plan_layout_host) return fail(TFEM_ERR_INVALID_ARGUMENT, "plan_layout_host is NULL");
+  RingLaunch L{coords, quad_order, alpha, beta, static_cast<const unsigned char *>(plan_device),
+               plan_layout_host, n_verts, nnz, vals, static_cast<hipStream_t>(stream)};
+  L.fq = fq;
+  L.source = source;
+  L.n_elems = n_elems;
+  L.fout = fout;
+  L.tile_first = tile_first;
+  L.tile_count = tile_count;
+  L.flags = flags;
+  if (const char *v = std::getenv("TFEM_RINGS_PER_CU")) L.blocks_per_cu = std::atoi(v);
+  return real_bytes == 8 ? launch_rings<double>(L) : launch_rings<float>(L);
+}
+
 }  // namespace tfem
 
 extern "C" {
@@ -441,19 +370,10 @@ int tfem_p1_assemble_rings(const void *coords, int real_bytes, int64_t n_verts, 
                            double alpha, double beta, const void *plan_device,
                            const int64_t *plan_layout_host, void *vals, int64_t nnz,
                            const void *fq, int64_t n_elems, void *fout, void *stream) {
-  using namespace tfem;
-  if (real_bytes != 4 && real_bytes != 8)
-    return fail(TFEM_ERR_INVALID_ARGUMENT, "real_bytes must be 4 or 8");
-  if (!plan_layout_host) return fail(TFEM_ERR_INVALID_ARGUMENT, "plan_layout_host is NULL");
-  RingLaunch L{coords, quad_order, alpha, beta, static_cast<const unsigned char *>(plan_device),
-               plan_layout_host, n_verts, nnz, vals, static_cast<hipStream_t>(stream)};
-  L.fq = fq;
-  L.n_elems = n_elems;
-  L.fout = fout;
-  // developer switches (tools/time_rings.py)
-  if (const char *v = std::getenv("TFEM_RINGS_PER_CU")) L.blocks_per_cu = std::atoi(v);
-  if (const char *v = std::getenv("TFEM_RINGS_DEBUG")) L.flags = std::atoi(v);  // ablation build
-  return real_bytes == 8 ? launch_rings<double>(L) : launch_rings<float>(L);
+  int flags = 0;
+  if (const char *v = std::getenv("TFEM_RINGS_DEBUG")) flags = std::atoi(v);  // ablation build
+  return tfem::ring_entry(coords, real_bytes, n_verts, quad_order, alpha, beta, plan_device, plan_layout_host, vals,
+                          nnz, fq, nullptr, n_elems, fout, 0, -1, flags, stream);
 }
 
 int tfem_p1_assemble_rings_source(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
@@ -461,17 +381,9 @@ int tfem_p1_assemble_rings_source(const void *coords, int real_bytes, int64_t n_
                                   const int64_t *plan_layout_host, void *vals, int64_t nnz,
                                   const tfem_source_program *source, int64_t n_elems, void *fout,
                                   void *stream) {
-  using namespace tfem;
-  if (real_bytes != 4 && real_bytes != 8)
-    return fail(TFEM_ERR_INVALID_ARGUMENT, "real_bytes must be 4 or 8");
-  if (!plan_layout_host || !source) return fail(TFEM_ERR_INVALID_ARGUMENT, "NULL pointer");
-  RingLaunch L{coords, quad_order, alpha, beta, static_cast<const unsigned char *>(plan_device),
-               plan_layout_host, n_verts, nnz, vals, static_cast<hipStream_t>(stream)};
-  L.source = source;
-  L.n_elems = n_elems;
-  L.fout = fout;
-  if (const char *v = std::getenv("TFEM_RINGS_PER_CU")) L.blocks_per_cu = std::atoi(v);
-  return real_bytes == 8 ? launch_rings<double>(L) : launch_rings<float>(L);
+  if (!source) return tfem::fail(TFEM_ERR_INVALID_ARGUMENT, "NULL pointer");
+  return tfem::ring_entry(coords, real_bytes, n_verts, quad_order, alpha, beta, plan_device, plan_layout_host, vals,
+                          nnz, nullptr, source, n_elems, fout, 0, -1, 0, stream);
 }
 
 int tfem_p1_assemble_rings_range(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
@@ -479,20 +391,8 @@ int tfem_p1_assemble_rings_range(const void *coords, int real_bytes, int64_t n_v
                                  const int64_t *plan_layout_host, void *vals, int64_t nnz, const void *fq,
                                  const tfem_source_program *source, int64_t n_elems, void *fout,
                                  int64_t tile_first, int64_t tile_count, void *stream) {
-  using namespace tfem;
-  if (real_bytes != 4 && real_bytes != 8)
-    return fail(TFEM_ERR_INVALID_ARGUMENT, "real_bytes must be 4 or 8");
-  if (!plan_layout_host) return fail(TFEM_ERR_INVALID_ARGUMENT, "plan_layout_host is NULL");
-  RingLaunch L{coords, quad_order, alpha, beta, static_cast<const unsigned char *>(plan_device),
-               plan_layout_host, n_verts, nnz, vals, static_cast<hipStream_t>(stream)};
-  L.fq = fq;
-  L.source = source;
-  L.n_elems = n_elems;
-  L.fout = fout;
-  L.tile_first = tile_first;
-  L.tile_count = tile_count;
-  if (const char *v = std::getenv("TFEM_RINGS_PER_CU")) L.blocks_per_cu = std::atoi(v);
-  return real_bytes == 8 ? launch_rings<double>(L) : launch_rings<float>(L);
+  return tfem::ring_entry(coords, real_bytes, n_verts, quad_order, alpha, beta, plan_device, plan_layout_host, vals,
+                          nnz, fq, source, n_elems, fout, tile_first, tile_count, 0, stream);
 }
 
 // Ablation build (fp64 stiffness, 7 slots) for tools/time_rings.py; `stamps` = 8 * 4 * grid

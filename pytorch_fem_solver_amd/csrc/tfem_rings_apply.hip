@@ -17,10 +17,6 @@
 // Plans with long rows (TFEM_RING_LONG=1: vertices with 8 .. 15 neighbours listed apart): the
 // tile launch skips those rows and k_p1_apply_long_rows forms them, sixteen lanes per row as in
 // k_p1_long_rows.
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-
 #include "tfem_rings_kernel.hpp"
 
 namespace tfem {
@@ -143,52 +139,18 @@ __global__ __launch_bounds__(kRingBlock) void k_p1_apply_rows(const RingArgs<T> 
   }
 }
 
-// Rows of vertices with 8 .. 15 neighbours (plans with long rows): sixteen lanes per row, lane i =
-// slot i of the fan, global ids; the entries are formed as in k_p1_long_rows and multiplied by u
-// of their columns, the products summed over the sixteen lanes.
+// Rows of vertices with 8 .. 15 neighbours (plans with long rows): sixteen lanes per row
+// (ring_long_slot); each slot lane multiplies its entry by u of its column, the products are
+// summed over the sixteen lanes and lane 0 writes y_v.
 template <typename T, bool MASS, bool DIAG>
 __global__ __launch_bounds__(kRingBlock) void k_p1_apply_long_rows(const T *coords, const unsigned char *plan,
                                                                    unsigned off_long, int n_long, const T *u, T *y,
                                                                    T stiff_w, T mass_d, T mass_o) {
-  const int gtid = int(blockIdx.x) * kRingBlock + int(threadIdx.x);
-  const int row = gtid >> 4, i = gtid & 15;
-  const bool live = row < n_long;
-  const uint32_t *rec = reinterpret_cast<const uint32_t *>(plan + off_long) + 24 * size_t(live ? row : 0);
-  const uint32_t v = rec[0];
-  const int k = int(rec[2] & 0xFFu);
-  const bool slot = live && i < k;
-  const uint32_t flag = slot ? (rec[3] >> (2 * i)) & 3u : 0u;
-  const int nxt = i + 1 == k ? 0 : i + 1;
-  const uint32_t g0 = rec[4 + (slot ? i : 0)], g1 = rec[4 + (slot ? nxt : 0)];
-  const T xv = coords[2 * size_t(v)], yv = coords[2 * size_t(v) + 1];
-  const T ecx = coords[2 * size_t(g0)] - xv, ecy = coords[2 * size_t(g0) + 1] - yv;
-  const T enx = coords[2 * size_t(g1)] - xv, eny = coords[2 * size_t(g1) + 1] - yv;
-  const T qc = ecx * ecx + ecy * ecy, qn = enx * enx + eny * eny;
-  const T p = ecx * enx + ecy * eny;
-  const T cross = ecx * eny - ecy * enx;
-  const T cs = flag_weight<T>(stiff_w, flag) * fast_rcp<T>(flag ? cross : T(1));
-  T here = cs * (p - qn), next = cs * (p - qc);  // to column n_i, to column n_next
-  T sdet = T(0);
-  if (MASS) {
-    sdet = flag_weight<T>(T(1), flag) * cross;
-    here = here + mass_o * sdet;
-    next = next + mass_o * sdet;
-  }
-  const int lane = int(threadIdx.x) & 63;
-  const int from = (lane & ~15) + (i == 0 ? (k > 0 ? k - 1 : 0) : i - 1);
-  const T entry = here + __shfl(next, from, 64);
-  T sum = here + next, dsum = sdet;
-  T prod = (!DIAG && slot) ? entry * u[g0] : T(0);
-#pragma unroll
-  for (int m = 8; m >= 1; m >>= 1) {
-    sum = sum + __shfl_xor(sum, m, 64);
-    if (MASS) dsum = dsum + __shfl_xor(dsum, m, 64);
-    if (!DIAG) prod = prod + __shfl_xor(prod, m, 64);
-  }
-  if (!live || i != 0) return;
-  // stiffness rows sum to zero; the mass part is taken out of the sum and added on the diagonal
-  const T diag = MASS ? mass_d * dsum - (sum - T(2) * mass_o * dsum) : -sum;
-  y[v] = DIAG ? diag : diag * u[v] + prod;
+  RingLongSlot<T> s;
+  ring_long_slot<T, MASS, !DIAG>(coords, plan, off_long, n_long, stiff_w, mass_o, u, s);
+  if (!s.live || s.i != 0) return;
+  const T diag = ring_diag<T, MASS>(s.sum, s.dsum, mass_d, mass_o);
+  y[s.v] = DIAG ? diag : diag * u[s.v] + s.prod;
 }
 
 template <typename T, int SLOTS, bool CHUNK>
@@ -207,19 +169,6 @@ static void *pick_apply_kernel(int slots, bool chunk, bool mass, bool diag) {
   return chunk ? pick_apply_diag<T, 15, true>(mass, diag) : pick_apply_diag<T, 15, false>(mass, diag);
 }
 
-static int apply_cu_count() {
-  static int cached = 0;
-  if (cached == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cached = prop.multiProcessorCount;
-    else
-      cached = 256;
-  }
-  return cached;
-}
-
 template <typename T>
 static int launch_apply(const void *coords, int64_t n_verts, int quad_order, double alpha, double beta,
                         const unsigned char *plan, const int64_t *z, const void *u, void *y, hipStream_t stream) {
@@ -228,88 +177,39 @@ static int launch_apply(const void *coords, int64_t n_verts, int quad_order, dou
     return fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
   if (z[0] == 0) return TFEM_OK;
   if (!coords || !plan || !y) return fail(TFEM_ERR_INVALID_ARGUMENT, "NULL pointer");
-  // the capacities the matrix launches check (tfem_rings.hip: launch_rings)
-  if (z[0] < 0 || z[4] > kRingBlock || z[3] > kRingVertCap || z[4] > z[3] || z[14] > kRingHaloCap ||
-      !((z[6] == 7 && z[7] == 4) || (z[6] == 15 && z[7] == 8)) || (z[5] > z[6] + 1 && z[23] == 0) || z[5] > 16)
-    return fail(TFEM_ERR_INVALID_ARGUMENT, "ring plan exceeds the kernel's capacities");
-  const int64_t rb = int64_t(sizeof(T));
-  const int64_t extents[3] = {n_verts * 2 * rb, z[12], n_verts * rb};
-  for (int64_t e : extents)
-    if (e < 0 || e >= (int64_t(1) << 32))
-      return fail(TFEM_ERR_INDEX_RANGE, "an array of %lld bytes does not fit the 32-bit offsets "
-                  "of the ring kernel", (long long)e);
   RingArgs<T> a;
-  std::memset(&a, 0, sizeof(a));
-  a.coords = static_cast<const T *>(coords);
-  a.plan = plan;
-  a.coords_bytes = unsigned(extents[0]);
-  a.plan_bytes = unsigned(extents[1]);
-  a.off_desc = unsigned(z[8]);
-  a.off_rows = unsigned(z[9]);
-  a.off_rowstart = unsigned(z[10]);
-  a.off_gid = unsigned(z[11]);
-  a.n_tiles = int(z[0]);
-  a.lds_vert = (int(z[3]) + 1) & ~1;
-  // W = sum_q w_q/2 and M_ij = sum_q (w_q/2) l_i l_j in T, in quadrature order: the same numbers
-  // the matrix launches use (tfem_rings.hip)
-  T w = T(0), md = T(0), mo = T(0);
-  for (int q = 0; q < tables.nq; ++q) {
-    w = w + T(tables.hw[q]);
-    md = md + T(tables.hw[q]) * (T(tables.lam[q][0]) * T(tables.lam[q][0]));
-    mo = mo + T(tables.hw[q]) * (T(tables.lam[q][0]) * T(tables.lam[q][1]));
-  }
-  a.stiff_w = T(alpha) * w;
-  a.mass_d = T(beta) * md;
-  a.mass_o = T(beta) * mo;
+  int st = ring_args_init<T>(tables, z, coords, plan, n_verts, alpha, beta, a);
+  if (st != TFEM_OK) return st;
+  const int64_t vec_bytes = n_verts * int64_t(sizeof(T));
+  st = check_extents("ring kernel", &vec_bytes, 1);
+  if (st != TFEM_OK) return st;
   ApplyArgs<T> b;
   b.u = static_cast<const T *>(u);
   b.y = static_cast<T *>(y);
-  b.u_bytes = u ? unsigned(extents[2]) : 0u;
-  b.y_bytes = unsigned(extents[2]);
+  b.u_bytes = u ? unsigned(vec_bytes) : 0u;
+  b.y_bytes = unsigned(vec_bytes);
   const bool mass = beta != 0.0, diag = u == nullptr, chunk = z[13] != 0;
   const int slots = int(z[6]);
   void *kernel = pick_apply_kernel<T>(slots, chunk, mass, diag);
   const size_t lds = size_t(3 * a.lds_vert) * sizeof(T);
-  // resident workgroups per CU, once per (kernel, LDS size): the launch path does no runtime query
-  struct Occupancy { void *kernel; size_t lds; int per_cu; };
-  static Occupancy occ_cache[32];
-  static int occ_used = 0;
-  static std::mutex occ_mutex;
   int per_cu = 0;
-  {
-    std::lock_guard<std::mutex> guard(occ_mutex);
-    for (int i = 0; i < occ_used; ++i)
-      if (occ_cache[i].kernel == kernel && occ_cache[i].lds == lds) per_cu = occ_cache[i].per_cu;
-    if (per_cu == 0) {
-      hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kRingBlock, lds);
-      if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-      if (occ_used < 32) occ_cache[occ_used++] = {kernel, lds, per_cu};
-    }
-  }
+  st = resident_per_cu(kernel, kRingBlock, lds, &per_cu);
+  if (st != TFEM_OK) return st;
   const int per = int((z[0] + 7) / 8);
-  const int blocks = std::min(per * 8, (apply_cu_count() * per_cu / 8) * 8);
+  const int blocks = std::min(per * 8, (device_cu_count() * per_cu / 8) * 8);
   void *params[] = {&a, &b};
   hipError_t e = hipLaunchKernel(kernel, dim3(unsigned(std::max(blocks, 8))), dim3(kRingBlock), params, lds, stream);
   if (e != hipSuccess) return fail(TFEM_ERR_HIP, "apply kernel launch: %s", hipGetErrorString(e));
   if (z[23] > 0) {  // the rows of the vertices with 8 .. 15 neighbours
     const dim3 lgrid{unsigned((16 * z[23] + kRingBlock - 1) / kRingBlock)};
-    const T *uu = static_cast<const T *>(u);
-    T *yy = static_cast<T *>(y);
-    const unsigned off_long = unsigned(z[22]);
-    const int n_long = int(z[23]);
-    if (mass && diag)
-      hipLaunchKernelGGL((k_p1_apply_long_rows<T, true, true>), lgrid, dim3(kRingBlock), 0, stream, a.coords, plan,
-                         off_long, n_long, uu, yy, a.stiff_w, a.mass_d, a.mass_o);
-    else if (mass)
-      hipLaunchKernelGGL((k_p1_apply_long_rows<T, true, false>), lgrid, dim3(kRingBlock), 0, stream, a.coords, plan,
-                         off_long, n_long, uu, yy, a.stiff_w, a.mass_d, a.mass_o);
-    else if (diag)
-      hipLaunchKernelGGL((k_p1_apply_long_rows<T, false, true>), lgrid, dim3(kRingBlock), 0, stream, a.coords, plan,
-                         off_long, n_long, uu, yy, a.stiff_w, a.mass_d, a.mass_o);
-    else
-      hipLaunchKernelGGL((k_p1_apply_long_rows<T, false, false>), lgrid, dim3(kRingBlock), 0, stream, a.coords, plan,
-                         off_long, n_long, uu, yy, a.stiff_w, a.mass_d, a.mass_o);
-    e = hipGetLastError();
+    void *long_kernel = mass ? (diag ? reinterpret_cast<void *>(k_p1_apply_long_rows<T, true, true>)
+                                     : reinterpret_cast<void *>(k_p1_apply_long_rows<T, true, false>))
+                             : (diag ? reinterpret_cast<void *>(k_p1_apply_long_rows<T, false, true>)
+                                     : reinterpret_cast<void *>(k_p1_apply_long_rows<T, false, false>));
+    unsigned off_long = unsigned(z[22]);
+    int n_long = int(z[23]);
+    void *long_params[] = {&a.coords, &a.plan, &off_long, &n_long, &b.u, &b.y, &a.stiff_w, &a.mass_d, &a.mass_o};
+    e = hipLaunchKernel(long_kernel, lgrid, dim3(kRingBlock), long_params, 0, stream);
     if (e != hipSuccess) return fail(TFEM_ERR_HIP, "long-row apply launch: %s", hipGetErrorString(e));
   }
   return TFEM_OK;

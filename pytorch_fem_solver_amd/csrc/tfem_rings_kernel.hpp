@@ -116,6 +116,16 @@ struct RingRec {
   }
 };
 
+// The diagonal of a row from the sum of its off-diagonal entries and, with mass, the sum of the
+// signed determinants around the vertex.  Stiffness rows sum to zero (constants are in the kernel
+// of the gradient): the diagonal is minus the sum of the off-diagonal stiffness entries.  With mass
+// the sum also holds the off-diagonal mass (M_ij det, twice per triangle): it is taken out again
+// before negating, and the diagonal mass is added.
+template <typename T, bool MASS>
+__device__ __forceinline__ T ring_diag(T sum, T dsum, T mass_d, T mass_o) {
+  return MASS ? mass_d * dsum - (sum - T(2) * mass_o * dsum) : -sum;
+}
+
 // The row of local vertex `lv`: entries of the neighbour slots in off[0 .. k), the diagonal in
 // diag (off[k ..] is scratch).  With q_i = |e_i|^2 and p = e_i.e_next the three entries of a
 // triangle are c (p - q_next), c (p - q_i) and their negative sum, c = +-W / (e_i x e_next); the
@@ -174,19 +184,11 @@ __device__ __forceinline__ void ring_row(const RingArgs<T> &a, const RingRec<SLO
   T wrapv = off[1];
 #pragma unroll
   for (int j = 2; j <= SLOTS; ++j) wrapv = k == j ? off[j] : wrapv;
-  // stiffness rows sum to zero (constants are in the kernel of the gradient): the diagonal is
-  // minus the sum of the off-diagonal stiffness entries; the mass part is added on top
   T sum = off[0];
 #pragma unroll
   for (int j = 1; j <= SLOTS; ++j) sum = sum + off[j];  // = sum_{j<k} off[j] + wrapv (once)
   off[0] = off[0] + wrapv;
-  if (MASS) {
-    // the sum above holds stiffness AND off-diagonal mass (M_ij det, twice per triangle): take
-    // the mass out again before negating, then add the diagonal mass
-    diag = a.mass_d * dsum - (sum - T(2) * a.mass_o * dsum);
-  } else {
-    diag = -sum;
-  }
+  diag = ring_diag<T, MASS>(sum, dsum, a.mass_d, a.mass_o);
 }
 
 // ring_row for a REGULAR row: six neighbours, six triangles, all of them stored counter-clockwise
@@ -235,10 +237,73 @@ __device__ __forceinline__ void ring_row_regular(const RingArgs<T> &a, const Rin
   for (int j = 1; j < 6; ++j) sum = sum + off[j];
   sum = (sum + wrapv) + T(0);  // off[6] = wrapv, off[7] = 0 in ring_row's sum
   off[0] = off[0] + wrapv;
-  if (MASS)
-    diag = a.mass_d * dsum - (sum - T(2) * a.mass_o * dsum);
-  else
-    diag = -sum;
+  diag = ring_diag<T, MASS>(sum, dsum, a.mass_d, a.mass_o);
+}
+
+// What ring_long_slot hands back to its lane.
+template <typename T>
+struct RingLongSlot {
+  const uint32_t *rec;  // the row's record
+  uint32_t v;           // the row's vertex (global id)
+  int i;                // the lane's slot
+  int dpos;             // position of the diagonal in the row's CSR values
+  bool live, slot;      // the row exists; slot i is one of its k neighbours
+  T entry;              // K[v][n_i] (slots only)
+  T sum, dsum;          // over the row's sixteen lanes: entries, signed determinants (ring_diag)
+  T prod;               // PROD: over the row's sixteen lanes, entry * u[n_i]
+};
+
+// One lane of a long row (plans with long rows, tfem_rings_host.cpp: 24-dword records of the
+// vertices with 8 .. 15 neighbours): SIXTEEN lanes per row, lane i = slot i of the fan,
+// coordinates by global ids.  The lane evaluates its slot's triangle (ring_row's formulas) and
+// takes what the previous slot's triangle adds to its own column from the lane before it (slot 0
+// from slot k - 1); the diagonal follows from the sums over the sixteen lanes (ring_diag).
+// k_p1_long_rows stores the entries; k_p1_apply_long_rows (PROD) also sums entry * u of the
+// column over the sixteen lanes, in the same pass.  `s` is filled in place rather than returned:
+// with a returned struct the long-row kernels took more VGPRs than before.
+template <typename T, bool MASS, bool PROD>
+__device__ __forceinline__ void ring_long_slot(const T *coords, const unsigned char *plan, unsigned off_long,
+                                               int n_long, T stiff_w, T mass_o, const T *u, RingLongSlot<T> &s) {
+  const int gtid = int(blockIdx.x) * kRingBlock + int(threadIdx.x);
+  const int row = gtid >> 4, i = gtid & 15;
+  s.i = i;
+  s.live = row < n_long;
+  const uint32_t *rec = reinterpret_cast<const uint32_t *>(plan + off_long) + 24 * size_t(s.live ? row : 0);
+  s.rec = rec;
+  const uint32_t v = rec[0];
+  s.v = v;
+  const int k = int(rec[2] & 0xFFu);
+  s.dpos = int(rec[2] >> 8);
+  s.slot = s.live && i < k;
+  const uint32_t flag = s.slot ? (rec[3] >> (2 * i)) & 3u : 0u;
+  const int nxt = i + 1 == k ? 0 : i + 1;
+  const uint32_t g0 = rec[4 + (s.slot ? i : 0)], g1 = rec[4 + (s.slot ? nxt : 0)];
+  const T xv = coords[2 * size_t(v)], yv = coords[2 * size_t(v) + 1];
+  const T ecx = coords[2 * size_t(g0)] - xv, ecy = coords[2 * size_t(g0) + 1] - yv;
+  const T enx = coords[2 * size_t(g1)] - xv, eny = coords[2 * size_t(g1) + 1] - yv;
+  const T qc = ecx * ecx + ecy * ecy, qn = enx * enx + eny * eny;
+  const T p = ecx * enx + ecy * eny;
+  const T cross = ecx * eny - ecy * enx;
+  const T cs = flag_weight<T>(stiff_w, flag) * fast_rcp<T>(flag ? cross : T(1));
+  T here = cs * (p - qn), next = cs * (p - qc);  // to column n_i, to column n_next
+  T sdet = T(0);
+  if (MASS) {
+    sdet = flag_weight<T>(T(1), flag) * cross;
+    here = here + mass_o * sdet;
+    next = next + mass_o * sdet;
+  }
+  const int lane = int(threadIdx.x) & 63;
+  const int from = (lane & ~15) + (i == 0 ? (k > 0 ? k - 1 : 0) : i - 1);
+  s.entry = here + __shfl(next, from, 64);
+  s.sum = here + next;
+  s.dsum = sdet;
+  s.prod = (PROD && s.slot) ? s.entry * u[g0] : T(0);
+#pragma unroll
+  for (int m = 8; m >= 1; m >>= 1) {
+    s.sum = s.sum + __shfl_xor(s.sum, m, 64);
+    if (MASS) s.dsum = s.dsum + __shfl_xor(s.dsum, m, 64);
+    if (PROD) s.prod = s.prod + __shfl_xor(s.prod, m, 64);
+  }
 }
 
 // Per-wave LDS stage: the wave's CSR entries, compact and in CSR order (row r of the wave
@@ -1143,5 +1208,43 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
 // wide: the three-elements-per-pass interpreter (programs of depth <= 2)
 template <typename T>
 void *pick_ring_src_kernel(int slots, bool mass, bool chunk, int nq, bool kmat, bool wide);
+
+// What every launch over a ring plan (layout z[], tfem_rings_host.cpp) sets alike: the capacity
+// check, the coordinate and plan extents, the section offsets, the tile count (the whole plan),
+// the LDS vertex slots and W / M_dd / M_od.  Every other field is zero.
+template <typename T>
+static int ring_args_init(const TriTables &tables, const int64_t *z, const void *coords, const unsigned char *plan,
+                   int64_t n_verts, double alpha, double beta, RingArgs<T> &a) {
+  if (z[0] < 0 || z[4] > kRingBlock || z[3] > kRingVertCap || z[4] > z[3] || z[14] > kRingHaloCap ||
+      !((z[6] == 7 && z[7] == 4) || (z[6] == 15 && z[7] == 8)) || (z[5] > z[6] + 1 && z[23] == 0) || z[5] > 16)
+    return fail(TFEM_ERR_INVALID_ARGUMENT, "ring plan exceeds the kernel's capacities");
+  const int64_t extents[2] = {n_verts * 2 * int64_t(sizeof(T)), z[12]};
+  const int st = check_extents("ring kernel", extents, 2);
+  if (st != TFEM_OK) return st;
+  std::memset(&a, 0, sizeof(a));
+  a.coords = static_cast<const T *>(coords);
+  a.plan = plan;
+  a.coords_bytes = unsigned(extents[0]);
+  a.plan_bytes = unsigned(extents[1]);
+  a.off_desc = unsigned(z[8]);
+  a.off_rows = unsigned(z[9]);
+  a.off_rowstart = unsigned(z[10]);
+  a.off_gid = unsigned(z[11]);
+  a.n_tiles = int(z[0]);
+  a.lds_vert = (int(z[3]) + 1) & ~1;
+  // W = sum_q w_q/2 and M_ij = sum_q (w_q/2) l_i l_j, formed in T in quadrature order.  The
+  // rules of element_tri.py:77-130 are symmetric, so M has one diagonal and one off-diagonal
+  // value (up to rounding: entries 00 and 01 are used).
+  T w = T(0), md = T(0), mo = T(0);
+  for (int q = 0; q < tables.nq; ++q) {
+    w = w + T(tables.hw[q]);
+    md = md + T(tables.hw[q]) * (T(tables.lam[q][0]) * T(tables.lam[q][0]));
+    mo = mo + T(tables.hw[q]) * (T(tables.lam[q][0]) * T(tables.lam[q][1]));
+  }
+  a.stiff_w = T(alpha) * w;
+  a.mass_d = T(beta) * md;
+  a.mass_o = T(beta) * mo;
+  return TFEM_OK;
+}
 
 }  // namespace tfem

@@ -634,19 +634,6 @@ struct TileLaunch {
   unsigned long long *stamps = nullptr;
 };
 
-static int cu_count() {
-  static int cached = 0;
-  if (cached == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cached = prop.multiProcessorCount;
-    else
-      cached = 256;
-  }
-  return cached;
-}
-
 // The ablation build exists for fp64 stiffness (K only, and K + f at Q = 4) alone.
 template <typename T, bool KMAT, bool MASS, int QL, bool REC8>
 static void *pick_kernel(bool dbg) {
@@ -697,10 +684,8 @@ static int launch_tiles(const TileLaunch &L) {
   const int64_t rb = int64_t(sizeof(T));
   const int64_t extents[5] = {L.n_verts * 2 * rb, z[19], L.n_elems * tables.nq * rb, L.nnz * rb,
                               L.n_verts * rb};
-  for (int64_t e : extents)
-    if (e < 0 || e >= (int64_t(1) << 32))
-      return fail(TFEM_ERR_INDEX_RANGE, "an array of %lld bytes does not fit the 32-bit offsets "
-                  "of the tile kernel", (long long)e);
+  const int st = check_extents("tile kernel", extents, 5);
+  if (st != TFEM_OK) return st;
   a.coords_bytes = unsigned(extents[0]);
   a.plan_bytes = unsigned(extents[1]);
   a.fq_bytes = load ? unsigned(extents[2]) : 0u;
@@ -744,7 +729,7 @@ static int launch_tiles(const TileLaunch &L) {
   // 4 resp. 6 waves per SIMD (register budget of the instantiation)
   const int cap = (load ? 4 : 6) * 256 / kTileBlock;
   per_cu = per_cu < 1 ? 1 : (per_cu > cap ? cap : per_cu);
-  int blocks = (cu_count() * per_cu / 8) * 8;
+  int blocks = (device_cu_count() * per_cu / 8) * 8;
   if (blocks > per * 8) blocks = per * 8;
   const dim3 grid{unsigned(blocks)}, block{unsigned(kTileBlock)};
   const bool dbg = L.flags >= 0;
