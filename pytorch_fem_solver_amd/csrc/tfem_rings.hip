@@ -20,8 +20,6 @@
 // values 28.6 B = 47.6 B, against 48 B algorithmic: the 16-byte row records replace the
 // 24 bytes of connectivity the row's triangles take.
 #include <cmath>
-#include <cstdio>
-#include <vector>
 
 #include "tfem_rings_kernel.hpp"
 
@@ -56,8 +54,6 @@ struct RingLaunch {
   const tfem_source_program *source = nullptr;  // load vector of this program instead of fq
   int64_t tile_first = 0, tile_count = -1;       // tile range of the plan (-1: to the end)
   int blocks_per_cu = 0;  // > 0: cap on resident workgroups per CU (tuning)
-  int flags = 0;          // > 0: ablation build (wrong results by design)
-  unsigned long long *stamps = nullptr;
 };
 
 // load vector alone (vals == NULL): the matrix part of the row is dead code
@@ -215,7 +211,6 @@ static int launch_rings(const RingLaunch &L) {
                      (src ? size_t(3 * (a.lds_vert + 2)) * sizeof(T)  // three buffers of sums per local vertex
                           : load ? size_t(3 * a.lds_elem + 4) * sizeof(T) : 0);
   const bool chunk = z[13] != 0;
-  a.flags = L.flags > 0 ? L.flags : 0;
   // Store policy of the CSR values (TFEM_RINGS_STORES=nt | plain overrides).  Measured at S(2236)
   // and S(3162) (profiles/r03_k_store_policy.log): the matrix-only launch from COLD caches (behind
   // 512 MB of unrelated reads) takes 81 us with plain stores against 99 us with non-temporal ones
@@ -224,25 +219,13 @@ static int launch_rings(const RingLaunch &L) {
   // the memory-side cache, prefer non-temporal stores (81-93 us against 100).  The launches that
   // also form a load vector are bound by vector issue and run 3-20 % faster with non-temporal
   // stores.  So: plain for the matrix alone, non-temporal with a load vector.
-  bool plain_stores = !load;
-  if (const char *v = std::getenv("TFEM_RINGS_STORES")) plain_stores = std::strcmp(v, "plain") == 0;
-  if (plain_stores) a.flags |= 1024;
-  a.stamps = L.stamps;
+  a.plain_stores = !load;
+  if (const char *v = std::getenv("TFEM_RINGS_STORES")) a.plain_stores = std::strcmp(v, "plain") == 0;
   // programs that never hold more than two values: three elements per pass of the interpreter
   bool wide = src && src_depth(L.source) <= 2;
   if (const char *v = std::getenv("TFEM_SRC_WIDE")) wide = wide && std::atoi(v) != 0;  // developer switch
   void *kernel = pick_ring_kernel<T>(slots, mass, chunk, load ? tables.nq : 0, src, kmat, wide);
   if (!kernel) return fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
-  if constexpr (sizeof(T) == 8) {  // the ablation build exists for fp64 stiffness, 7 slots
-    if (kmat && !src && L.flags > 0 && slots == 7 && !mass && (!load || tables.nq == 4)) {
-      if (load)
-        kernel = chunk ? reinterpret_cast<void *>(k_p1_rings<T, 7, false, true, 4, true>)
-                       : reinterpret_cast<void *>(k_p1_rings<T, 7, false, false, 4, true>);
-      else
-        kernel = chunk ? reinterpret_cast<void *>(k_p1_rings<T, 7, false, true, 0, true>)
-                       : reinterpret_cast<void *>(k_p1_rings<T, 7, false, false, 0, true>);
-    }
-  }
   // resident workgroups: what LDS and registers allow per CU, on every CU
   int per_cu = 0;
   st = resident_per_cu(kernel, kRingBlock, lds, &per_cu);
@@ -262,61 +245,9 @@ static int launch_rings(const RingLaunch &L) {
   if (const char *v = std::getenv("TFEM_RINGS_RESERVE_CUS")) cus = std::max(8, cus - 8 * std::max(0, std::atoi(v)));
   const int blocks = std::min(per * 8, (cus * per_cu / 8) * 8);
   const dim3 grid{unsigned(blocks)}, block{unsigned(kRingBlock)};
-#ifdef TFEM_SRC_TIMING
-  // developer build (tools/ablate_src.py): phase stamps of launch number 300 of a source program
-  static unsigned long long *dev_stamps = nullptr;
-  static int n_launch = 0;
-  const bool stamp_now = src && kmat && ++n_launch == 300;
-  if (stamp_now) {
-    if (!dev_stamps) (void)hipMalloc(&dev_stamps, sizeof(unsigned long long) * 12 * kRingWaves * 8192);
-    a.stamps = dev_stamps;
-  }
-#endif
   void *params[] = {&a};
   hipError_t e = hipLaunchKernel(kernel, grid, block, params, lds, L.stream);
   if (e != hipSuccess) return fail(TFEM_ERR_HIP, "ring kernel launch: %s", hipGetErrorString(e));
-#ifdef TFEM_SRC_TIMING
-  if (stamp_now) {
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h(size_t(12) * kRingWaves * size_t(blocks));
-    (void)hipMemcpy(h.data(), dev_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    double sum[10] = {0};
-    double clk = 0, real = 0, real_max = 0, real_min = 1e300, tiles_max = 0;
-    for (size_t w = 0; w < size_t(kRingWaves) * size_t(blocks); ++w) {
-      for (int i = 0; i < 10; ++i) sum[i] += double(h[12 * w + size_t(i)]);
-      clk += double(h[12 * w + 10]);
-      real += double(h[12 * w + 11]);
-      real_max = std::max(real_max, double(h[12 * w + 11]));
-      real_min = std::min(real_min, double(h[12 * w + 11]));
-      tiles_max = std::max(tiles_max, double(h[12 * w + 7]));
-    }
-    const char *names[10] = {"A loads", "B rows", "stage", "vmcnt", "park", "stores", "barrier E", "tiles", "G", "barrier G"};
-    std::fprintf(stderr, "[stamps] %d workgroups, shader cycles per tile and wave (s_memtime):", blocks);
-    for (int i = 0; i < 10; ++i)
-      if (i != 7) std::fprintf(stderr, "  %s %.0f", names[i], sum[i] / sum[7]);
-    std::fprintf(stderr, "  tiles/wave %.1f  |  in-kernel clock %.3f GHz (shader cycles / 100 MHz ticks over the waves' tile loops), loop %.1f us\n",
-                 sum[7] / (double(kRingWaves) * blocks), clk / real * 0.1, real / (double(kRingWaves) * blocks) * 0.01);
-    std::fprintf(stderr, "[stamps] loop of the shortest / longest wave %.1f / %.1f us, most tiles of a wave %.0f\n",
-                 real_min * 0.01, real_max * 0.01, tiles_max);
-    // who is fast: mean loop by the workgroup's place in the launch order (blocks of 256 = one per CU)
-    // and by XCD
-    std::fprintf(stderr, "[stamps] mean loop by blockIdx / 256:");
-    for (int layer = 0; layer * 256 < blocks; ++layer) {
-      double t = 0;
-      int n = 0;
-      for (int b = layer * 256; b < std::min(blocks, (layer + 1) * 256); ++b, ++n) t += double(h[12 * size_t(b) * kRingWaves + 11]);
-      std::fprintf(stderr, " %.1f", t / n * 0.01);
-    }
-    std::fprintf(stderr, " us;  by XCD (blockIdx & 7):");
-    for (int x = 0; x < 8; ++x) {
-      double t = 0;
-      int n = 0;
-      for (int b = x; b < blocks; b += 8, ++n) t += double(h[12 * size_t(b) * kRingWaves + 11]);
-      std::fprintf(stderr, " %.1f", t / n * 0.01);
-    }
-    std::fprintf(stderr, " us\n");
-  }
-#endif
   if (kmat && z[23] > 0) {  // the rows of the vertices with 8 .. 15 neighbours
     const dim3 lgrid{unsigned((16 * z[23] + kRingBlock - 1) / kRingBlock)};  // sixteen lanes per row
     if (mass)
@@ -332,11 +263,11 @@ static int launch_rings(const RingLaunch &L) {
 }
 
 // The exported launches (tfem_p1_assemble_rings*): argument checks, the launch description and
-// the developer switch TFEM_RINGS_PER_CU (tools/time_rings.py).  flags > 0: ablation build.
+// the developer switch TFEM_RINGS_PER_CU (tools/time_rings.py).
 static int ring_entry(const void *coords, int real_bytes, int64_t n_verts, int quad_order, double alpha,
                       double beta, const void *plan_device, const int64_t *plan_layout_host, void *vals,
                       int64_t nnz, const void *fq, const tfem_source_program *source, int64_t n_elems,
-                      void *fout, int64_t tile_first, int64_t tile_count, int flags, void *stream) {
+                      void *fout, int64_t tile_first, int64_t tile_count, void *stream) {
   if (real_bytes != 4 && real_bytes != 8)
     return fail(TFEM_ERR_INVALID_ARGUMENT, "real_bytes must be 4 or 8");
   if (!plan_layout_host) return fail(TFEM_ERR_INVALID_ARGUMENT, "plan_layout_host is NULL");
@@ -348,7 +279,6 @@ static int ring_entry(const void *coords, int real_bytes, int64_t n_verts, int q
   L.fout = fout;
   L.tile_first = tile_first;
   L.tile_count = tile_count;
-  L.flags = flags;
   if (const char *v = std::getenv("TFEM_RINGS_PER_CU")) L.blocks_per_cu = std::atoi(v);
   return real_bytes == 8 ? launch_rings<double>(L) : launch_rings<float>(L);
 }
@@ -370,10 +300,8 @@ int tfem_p1_assemble_rings(const void *coords, int real_bytes, int64_t n_verts, 
                            double alpha, double beta, const void *plan_device,
                            const int64_t *plan_layout_host, void *vals, int64_t nnz,
                            const void *fq, int64_t n_elems, void *fout, void *stream) {
-  int flags = 0;
-  if (const char *v = std::getenv("TFEM_RINGS_DEBUG")) flags = std::atoi(v);  // ablation build
   return tfem::ring_entry(coords, real_bytes, n_verts, quad_order, alpha, beta, plan_device, plan_layout_host, vals,
-                          nnz, fq, nullptr, n_elems, fout, 0, -1, flags, stream);
+                          nnz, fq, nullptr, n_elems, fout, 0, -1, stream);
 }
 
 int tfem_p1_assemble_rings_source(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
@@ -383,7 +311,7 @@ int tfem_p1_assemble_rings_source(const void *coords, int real_bytes, int64_t n_
                                   void *stream) {
   if (!source) return tfem::fail(TFEM_ERR_INVALID_ARGUMENT, "NULL pointer");
   return tfem::ring_entry(coords, real_bytes, n_verts, quad_order, alpha, beta, plan_device, plan_layout_host, vals,
-                          nnz, nullptr, source, n_elems, fout, 0, -1, 0, stream);
+                          nnz, nullptr, source, n_elems, fout, 0, -1, stream);
 }
 
 int tfem_p1_assemble_rings_range(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
@@ -392,25 +320,7 @@ int tfem_p1_assemble_rings_range(const void *coords, int real_bytes, int64_t n_v
                                  const tfem_source_program *source, int64_t n_elems, void *fout,
                                  int64_t tile_first, int64_t tile_count, void *stream) {
   return tfem::ring_entry(coords, real_bytes, n_verts, quad_order, alpha, beta, plan_device, plan_layout_host, vals,
-                          nnz, fq, source, n_elems, fout, tile_first, tile_count, 0, stream);
-}
-
-// Ablation build (fp64 stiffness, 7 slots) for tools/time_rings.py; `stamps` = 8 * 4 * grid
-// 64-bit words or NULL.
-int tfem_p1_rings_debug(const void *coords, int64_t n_verts, int quad_order, const void *plan_device,
-                        const int64_t *plan_layout_host, void *vals, int64_t nnz, void *stream,
-                        int flags, int blocks_per_cu, unsigned long long *stamps, const void *fq,
-                        int64_t n_elems, void *fout) {
-  using namespace tfem;
-  RingLaunch L{coords, quad_order, 1.0, 0.0, static_cast<const unsigned char *>(plan_device),
-               plan_layout_host, n_verts, nnz, vals, static_cast<hipStream_t>(stream)};
-  L.flags = flags;
-  L.blocks_per_cu = blocks_per_cu;
-  L.stamps = stamps;
-  L.fq = fq;
-  L.n_elems = n_elems;
-  L.fout = fout;
-  return launch_rings<double>(L);
+                          nnz, fq, source, n_elems, fout, tile_first, tile_count, stream);
 }
 
 }  // extern "C"

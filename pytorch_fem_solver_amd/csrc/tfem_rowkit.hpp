@@ -26,12 +26,9 @@ typedef const int32_t __attribute__((address_space(4))) *ring_const_i32;
 // (Neutral for the fused K + f launch; the P2 row kernels and the tile kernel are 5-10 % slower
 // with it and keep plain stores.)
 constexpr int kStreamNT = 2;
-// The same hint on the read-once plan streams (row records, slot codes, element ids, source
-// values); build with -DTFEM_NT_LOADS=0 to compare.
-#ifndef TFEM_NT_LOADS
-#define TFEM_NT_LOADS 0
-#endif
-constexpr int kStreamLoadNT = TFEM_NT_LOADS ? 2 : 0;
+// Cache policy of the read-once plan streams (row records, slot codes, element ids): plain loads,
+// without that hint (2 would set it).
+constexpr int kStreamLoadNT = 0;
 
 template <typename T>
 __device__ __forceinline__ T fast_rcp(T x) {

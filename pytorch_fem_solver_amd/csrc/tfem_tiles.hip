@@ -44,10 +44,7 @@ namespace tfem {
 
 // 512 lanes (8 waves) share one tile: with two workgroups per CU that is 4 waves per SIMD,
 // which is what hides the dependent fp64 / LDS latency chains of the element phase.
-#ifndef TFEM_TILE_BLOCK
-#define TFEM_TILE_BLOCK 512
-#endif
-constexpr int kTileBlock = TFEM_TILE_BLOCK;
+constexpr int kTileBlock = 512;
 constexpr int kWaves = kTileBlock / 64;
 constexpr int kElemPerLane = 2;  // tile element capacity   = 1024: two full rounds, all 8
                                  // waves equally loaded (the plan fills tiles up to it)
@@ -138,8 +135,6 @@ struct TileArgs {
   T stiff_w;     // alpha * sum_q w_q / 2
   T mass_w[6];   // beta * sum_q (w_q/2) l_i l_j for (i,j) = 00 01 02 11 12 22
   T lamw[kMaxQuad][3];  // l_i(q) * w_q / 2
-  int flags;     // diagnostic build only (tfem_p1_tiles_debug)
-  unsigned long long *stamps;  // diagnostic build, flag 16: 8 cycle sums per wave
 };
 
 struct TileDesc {
@@ -157,13 +152,6 @@ __device__ __forceinline__ TileDesc load_desc(const int32_t *desc, int tile) {
   return TileDesc{d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9]};
 }
 
-// Diagnostic build only: shader-clock stamp (cdna_hip_programming.md section 7).
-__device__ __forceinline__ unsigned long long stamp() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-
 // LDS-only workgroup barrier: outstanding global loads (the prefetch) stay in flight.
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -177,7 +165,7 @@ __device__ __forceinline__ void lds_barrier() {
 // vertices) map to a small trash area that is never written out, so the element phase has
 // no branches.  Padding lanes hold a null record (a dummy vertex whose row is trash too).
 // `srcw[i]` = sum_q f_q l_i(q) w_q/2 of this element (load vector).
-template <typename T, bool KMAT, bool MASS, bool LOAD, bool REC8, bool DBG>
+template <typename T, bool KMAT, bool MASS, bool LOAD, bool REC8>
 __device__ __forceinline__ void element_to_lds(const TileArgs<T> &a, const uint32_t (&rec)[3],
                                                const T (&srcw)[3], const unsigned char *xy_bytes,
                                                const unsigned char *loff_bytes,
@@ -223,11 +211,7 @@ __device__ __forceinline__ void element_to_lds(const TileArgs<T> &a, const uint3
         const int pos = REC8 ? int((rec[1] >> (3 * (3 * j + i))) & 0x7u)
                              : int((rec[j] >> (16 + 4 * i)) & 0xFu);
         T *slot = reinterpret_cast<T *>(acc_bytes + base[j] + pos * int(sizeof(T)));
-        if (DBG && (a.flags & 1)) {
-          if (loc[i][j] == T(-1.2345e300)) *slot = loc[i][j];  // keeps the math alive
-        } else {
-          atomicAdd(slot, loc[i][j]);  // ds_add_f64 / ds_add_f32
-        }
+        atomicAdd(slot, loc[i][j]);  // ds_add_f64 / ds_add_f32
       }
     }
   }
@@ -265,12 +249,8 @@ __device__ __forceinline__ void element_to_lds(const TileArgs<T> &a, const uint3
 // front of loops); no select between an LDS value and a register value (it can become a
 // flat_load, which waits on vmcnt too); registers written by loads are only ever read
 // right after the explicit wait (copied if they must live longer).
-// DBG = true is the ablation build used by tools/ablate_tiles.py: bits of a.flags switch
-// off 1 = LDS atomics, 2 = the whole element phase, 4 = the value stores, 8 = the
-// coordinate gather, 16 = in-kernel stamps.  Its results are wrong by design; the product
-// path never uses it.
 // ---------------------------------------------------------------------------------------
-template <typename T, bool KMAT, bool MASS, int QL, bool REC8, bool DBG>
+template <typename T, bool KMAT, bool MASS, int QL, bool REC8>
 __global__ __launch_bounds__(kTileBlock, QL > 0 ? 4 : 6) void k_p1_tiles_pipe(const TileArgs<T> a) {
   constexpr bool LOAD = QL > 0;
   static_assert(!REC8 || kElemPerLane == 2, "8-byte records are loaded two per lane");
@@ -360,11 +340,9 @@ __global__ __launch_bounds__(kTileBlock, QL > 0 ? 4 : 6) void k_p1_tiles_pipe(co
       runl_ld[r] = int(__builtin_amdgcn_raw_buffer_load_b16(r_plan, a.off_runl + (unsigned(d.lrun_off) + l) * 2u, 0, 0));
       rund_ld[r] = int(__builtin_amdgcn_raw_buffer_load_b32(r_plan, a.off_rund + (unsigned(d.run_off) + l) * 4u, 0, 0));
     }
-    if (!(DBG && (a.flags & 8))) {
 #pragma unroll
-      for (int v = 0; v < kVertPerLane; ++v)
-        buf_load2<T>(r_coords, unsigned(gid[v]) * unsigned(2 * sizeof(T)), xy_ld[v][0], xy_ld[v][1]);
-    }
+    for (int v = 0; v < kVertPerLane; ++v)
+      buf_load2<T>(r_coords, unsigned(gid[v]) * unsigned(2 * sizeof(T)), xy_ld[v][0], xy_ld[v][1]);
     if (LOAD) {
 #pragma unroll
       for (int e = 0; e < kElemPerLane; ++e) {
@@ -481,37 +459,24 @@ __global__ __launch_bounds__(kTileBlock, QL > 0 ? 4 : 6) void k_p1_tiles_pipe(co
   build_chunks(dc, 0);
   __syncthreads();
 
-  if (DBG && (a.flags & 32)) {  // experiment: spread the workgroups' phases over one tile period
-    const int steps = (blockIdx.x >> 3) & 15;
-    for (int i = 0; i < steps; ++i) __builtin_amdgcn_s_sleep(15);  // ~1000 cycles per step
-  }
   int cur = 0;   // run / chunk-table buffer of the current tile
   int slot = 0;  // k mod 3: vertex-id buffer of the current tile
-  unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int k = 0;; ++k) {
     const int *runl = runl_buf + cur * a.lds_run;
     const int *rund = rund_buf + cur * a.lds_run;
-    const bool timing = DBG && (a.flags & 16);
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
-    if (timing) t0 = stamp();
     // ---- S2 ----------------------------------------------------------------------------------
-    if (!(DBG && (a.flags & 2))) {
-      // waves whose 64 slots of a round lie past the end of the tile skip the round (scalar
-      // branch); inside the last partial wave the padding lanes process null records
+    // waves whose 64 slots of a round lie past the end of the tile skip the round (scalar
+    // branch); inside the last partial wave the padding lanes process null records
 #pragma unroll
-      for (int e = 0; e < kElemPerLane; ++e) {
-        if ((REC8 ? 128 * wave + e : e * kTileBlock + wave * 64) < dc.n_elem)
-          element_to_lds<T, KMAT, MASS, LOAD, REC8, DBG>(
-              a, rec[e], srcw[e], reinterpret_cast<const unsigned char *>(xy),
-              reinterpret_cast<const unsigned char *>(loff), reinterpret_cast<unsigned char *>(acc),
-              dc.n_own, facc0, trash);
-      }
+    for (int e = 0; e < kElemPerLane; ++e) {
+      if ((REC8 ? 128 * wave + e : e * kTileBlock + wave * 64) < dc.n_elem)
+        element_to_lds<T, KMAT, MASS, LOAD, REC8>(
+            a, rec[e], srcw[e], reinterpret_cast<const unsigned char *>(xy),
+            reinterpret_cast<const unsigned char *>(loff), reinterpret_cast<unsigned char *>(acc),
+            dc.n_own, facc0, trash);
     }
-    if (timing) t1 = stamp();
     lds_barrier();
-    if (timing) t2 = stamp();
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see the comment above the kernel
-    if (timing) t3 = stamp();
     // ---- S5 ----------------------------------------------------------------------------------
     // wave w streams chunks w, w+8, ...: lane l owns accumulator entries 128c + 2l, + 2l + 1;
     // their run (hence their place in the CSR array) comes from the chunk table.  Both in one
@@ -529,17 +494,12 @@ __global__ __launch_bounds__(kTileBlock, QL > 0 ? 4 : 6) void k_p1_tiles_pipe(co
           if (!(tab.w >> 16)) {
             const int d0 = s0 < tab.x ? tab.y : tab.z;
             const int d1 = s0 + 1 < tab.x ? tab.y : tab.z;
-            unsigned long long ts0 = 0;
-            if (timing) ts0 = stamp();
-            if (!(DBG && (a.flags & 4))) {
-              if (d0 == d1 && s0 + 1 < dc.acc_size) {
-                buf_store2<T>(r_vals, (unsigned(s0 + d0) * unsigned(sizeof(T))) & ((DBG && (a.flags & 64)) ? 0xFFFF0u : ~0u), v0, v1);
-              } else {  // the pair straddles two runs, or is the odd tail
-                if (s0 < dc.acc_size) buf_store1<T>(r_vals, unsigned(s0 + d0) * unsigned(sizeof(T)), v0);
-                if (s0 + 1 < dc.acc_size) buf_store1<T>(r_vals, unsigned(s0 + 1 + d1) * unsigned(sizeof(T)), v1);
-              }
+            if (d0 == d1 && s0 + 1 < dc.acc_size) {
+              buf_store2<T>(r_vals, unsigned(s0 + d0) * unsigned(sizeof(T)), v0, v1);
+            } else {  // the pair straddles two runs, or is the odd tail
+              if (s0 < dc.acc_size) buf_store1<T>(r_vals, unsigned(s0 + d0) * unsigned(sizeof(T)), v0);
+              if (s0 + 1 < dc.acc_size) buf_store1<T>(r_vals, unsigned(s0 + 1 + d1) * unsigned(sizeof(T)), v1);
             }
-            if (timing) tsum[7] += stamp() - ts0;  // cycles inside the store statements (fast chunks)
           } else {  // more than two runs meet in this chunk: each entry searches the next 128
             // runs with a fixed-trip binary search (no loop: hipcc drains vmcnt before loops)
             int lo0 = tab.w & 0xFFFF, lo1 = lo0;
@@ -555,10 +515,8 @@ __global__ __launch_bounds__(kTileBlock, QL > 0 ? 4 : 6) void k_p1_tiles_pipe(co
               hi1 = (g1 && st1 > s0 + 1) ? m1 : hi1;
             }
             const int e0 = rund[lo0], e1 = rund[lo1];
-            if (!(DBG && (a.flags & 4))) {
-              if (s0 < dc.acc_size) buf_store1<T>(r_vals, unsigned(s0 + e0) * unsigned(sizeof(T)), v0);
-              if (s0 + 1 < dc.acc_size) buf_store1<T>(r_vals, unsigned(s0 + 1 + e1) * unsigned(sizeof(T)), v1);
-            }
+            if (s0 < dc.acc_size) buf_store1<T>(r_vals, unsigned(s0 + e0) * unsigned(sizeof(T)), v0);
+            if (s0 + 1 < dc.acc_size) buf_store1<T>(r_vals, unsigned(s0 + 1 + e1) * unsigned(sizeof(T)), v1);
           }
           if (s0 < dc.acc_size) {  // never clear beyond the tile's entries (+1: rounding slack)
             acc[s0] = T(0);
@@ -574,31 +532,18 @@ __global__ __launch_bounds__(kTileBlock, QL > 0 ? 4 : 6) void k_p1_tiles_pipe(co
       for (int r = 0; r < kRowPerLane; ++r) {
         const int l = tid + r * kTileBlock;
         if (l < dc.n_own) {
-          if (!(DBG && (a.flags & 4)))
-            buf_store1<T>(r_fout, unsigned(gid_r[l]) * unsigned(sizeof(T)), facc[l]);
+          buf_store1<T>(r_fout, unsigned(gid_r[l]) * unsigned(sizeof(T)), facc[l]);
           facc[l] = T(0);
         }
       }
     }
-    if (timing) t4 = stamp();
     // ---- S3 + S4 ---------------------------------------------------------------------------------
     if (t_n >= 0) take_tile(dn, cur ^ 1);
     if (t_nn >= 0) {
       load_tile(dnn, slot == 0 ? 2 : slot - 1);  // (k + 2) mod 3
       if (t_nnn >= 0) load_ids(dnnn);
     }
-    if (timing) t5 = stamp();
     lds_barrier();
-    if (timing) {
-      t6 = stamp();
-      tsum[0] += t1 - t0;  // S2 element phase
-      tsum[1] += t2 - t1;  // barrier after S2
-      tsum[2] += t3 - t2;  // vmcnt(0)
-      tsum[3] += t5 - t4;  // S3 + S4
-      tsum[4] += t4 - t3;  // S5
-      tsum[5] += t6 - t5;  // barrier after S3/S4
-      tsum[6] += 1;
-    }
     if (t_n < 0) break;
     build_chunks(dn, cur ^ 1);  // visible to S5 of the next tile through the barrier after its S2
     // ---- advance the tile window --------------------------------------------------------------
@@ -613,10 +558,6 @@ __global__ __launch_bounds__(kTileBlock, QL > 0 ? 4 : 6) void k_p1_tiles_pipe(co
     cur ^= 1;
     slot = slot == 2 ? 0 : slot + 1;
   }
-  if (DBG && (a.flags & 16) && a.stamps && (tid & 63) == 0) {
-    unsigned long long *o = a.stamps + 8 * (size_t(blockIdx.x) * kWaves + (tid >> 6));
-    for (int i = 0; i < 8; ++i) o[i] = tsum[i];
-  }
 }
 
 struct TileLaunch {
@@ -630,35 +571,24 @@ struct TileLaunch {
   const void *fq;   // nullptr: no load vector
   void *fout;
   hipStream_t stream;
-  int flags = -1;   // >= 0: diagnostic build
-  unsigned long long *stamps = nullptr;
 };
 
-// The ablation build exists for fp64 stiffness (K only, and K + f at Q = 4) alone.
-template <typename T, bool KMAT, bool MASS, int QL, bool REC8>
-static void *pick_kernel(bool dbg) {
-  if constexpr (sizeof(T) == 8 && KMAT && !MASS && (QL == 0 || QL == 4)) {
-    if (dbg) return reinterpret_cast<void *>(k_p1_tiles_pipe<T, KMAT, MASS, QL, REC8, true>);
-  }
-  return reinterpret_cast<void *>(k_p1_tiles_pipe<T, KMAT, MASS, QL, REC8, false>);
-}
-
 template <typename T, bool KMAT, bool MASS, bool REC8>
-static void *pick_q(int nq, bool load, bool dbg) {
-  if (!load) return pick_kernel<T, KMAT, MASS, 0, REC8>(dbg);
+static void *pick_q(int nq, bool load) {
+  if (!load) return reinterpret_cast<void *>(k_p1_tiles_pipe<T, KMAT, MASS, 0, REC8>);
   switch (nq) {
-    case 1: return pick_kernel<T, KMAT, MASS, 1, REC8>(dbg);
-    case 3: return pick_kernel<T, KMAT, MASS, 3, REC8>(dbg);
-    case 4: return pick_kernel<T, KMAT, MASS, 4, REC8>(dbg);
-    case 6: return pick_kernel<T, KMAT, MASS, 6, REC8>(dbg);
+    case 1: return reinterpret_cast<void *>(k_p1_tiles_pipe<T, KMAT, MASS, 1, REC8>);
+    case 3: return reinterpret_cast<void *>(k_p1_tiles_pipe<T, KMAT, MASS, 3, REC8>);
+    case 4: return reinterpret_cast<void *>(k_p1_tiles_pipe<T, KMAT, MASS, 4, REC8>);
+    case 6: return reinterpret_cast<void *>(k_p1_tiles_pipe<T, KMAT, MASS, 6, REC8>);
     default: return nullptr;
   }
 }
 
 template <typename T, bool REC8>
-static void *pick_form(bool kmat, bool mass, int nq, bool load, bool dbg) {
-  if (!kmat) return pick_q<T, false, false, REC8>(nq, true, dbg);
-  return mass ? pick_q<T, true, true, REC8>(nq, load, dbg) : pick_q<T, true, false, REC8>(nq, load, dbg);
+static void *pick_form(bool kmat, bool mass, int nq, bool load) {
+  if (!kmat) return pick_q<T, false, false, REC8>(nq, true);
+  return mass ? pick_q<T, true, true, REC8>(nq, load) : pick_q<T, true, false, REC8>(nq, load);
 }
 
 template <typename T>
@@ -702,8 +632,6 @@ static int launch_tiles(const TileLaunch &L) {
   a.lds_vert = int(z[6]) | 1;  // odd: lds_vert + 1 is even, every LDS array stays 8-byte aligned
   a.lds_own = load ? ((int(z[7]) + 3) & ~3) : 0;
   a.lds_run = (int(z[10]) + 2) & ~1;  // even: the int4 chunk table behind it stays aligned
-  a.flags = L.flags < 0 ? 0 : L.flags;
-  a.stamps = L.stamps;
   // W = sum_q w_q/2, M_ij = sum_q (w_q/2) l_i l_j, l_i(q) w_q/2: formed in T, quadrature order
   T w = T(0);
   for (int q = 0; q < tables.nq; ++q) w = w + T(tables.hw[q]);
@@ -732,14 +660,13 @@ static int launch_tiles(const TileLaunch &L) {
   int blocks = (device_cu_count() * per_cu / 8) * 8;
   if (blocks > per * 8) blocks = per * 8;
   const dim3 grid{unsigned(blocks)}, block{unsigned(kTileBlock)};
-  const bool dbg = L.flags >= 0;
   const bool mass = kmat && L.beta != 0.0;
   if (z[20] != 2 && z[20] != 3)
     return fail(TFEM_ERR_INVALID_ARGUMENT, "plan layout: %lld words per record", (long long)z[20]);
   if (z[20] == 2 && (kElemPerLane != 2 || z[6] > 1022))
     return fail(TFEM_ERR_INVALID_ARGUMENT, "8-byte records need <= 1022 vertices per tile");
-  void *kernel = z[20] == 2 ? pick_form<T, true>(kmat, mass, tables.nq, load, dbg)
-                            : pick_form<T, false>(kmat, mass, tables.nq, load, dbg);
+  void *kernel = z[20] == 2 ? pick_form<T, true>(kmat, mass, tables.nq, load)
+                            : pick_form<T, false>(kmat, mass, tables.nq, load);
   if (!kernel) return fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
@@ -791,21 +718,6 @@ int tfem_p1_assemble_tiles(const void *coords, int real_bytes, int64_t n_verts, 
                plan_layout_host, n_verts, n_elems, nnz, vals, fq, fout,
                static_cast<hipStream_t>(stream)};
   return real_bytes == 8 ? launch_tiles<double>(L) : launch_tiles<float>(L);
-}
-
-// Ablation build (fp64) for tools/ablate_tiles.py.
-int tfem_p1_tiles_debug(const void *coords, int64_t n_verts, int quad_order,
-                        const void *plan_device, const int64_t *plan_layout_host, void *vals,
-                        int64_t nnz, const void *fq, int64_t n_elems, void *fout, void *stream,
-                        int flags, unsigned long long *stamps) {
-  using namespace tfem;
-  const int64_t *z = plan_layout_host;
-  if (int st = check_plan_limits(z[0], int(z[5]), int(z[6]), int(z[7]), int(z[8]), int(z[10])))
-    return st;
-  TileLaunch L{coords, quad_order, 1.0, 0.0, static_cast<const unsigned char *>(plan_device),
-               plan_layout_host, n_verts, n_elems, nnz, vals, fq, fout,
-               static_cast<hipStream_t>(stream), flags & 0xFF, stamps};
-  return launch_tiles<double>(L);
 }
 
 }  // extern "C"

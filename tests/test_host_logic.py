@@ -4,6 +4,8 @@ mesh topology against the reference-generated fixtures.  No GPU compute is calle
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -42,6 +44,13 @@ def test_library_loads_and_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in tfem_assembly.h but not exported"
         assert name in _native.SIGNATURES, f"{name} has no ctypes signature"
+    # the converse: every exported tfem_* symbol is declared (no undeclared hooks)
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    listing = subprocess.run([nm, "-D", "--defined-only", _native.LIB_PATH], check=True,
+                             capture_output=True, text=True).stdout
+    symbols = [line.split()[-1] for line in listing.splitlines() if line.strip()]
+    exported = {name for name in symbols if name.startswith("tfem_")}
+    assert exported == declared, f"exported but not declared: {sorted(exported - declared)}"
     assert lib.tfem_abi_version() == _native.ABI_VERSION
     version = int(re.search(r"#define TFEM_ABI_VERSION (\d+)", header).group(1))
     assert version == _native.ABI_VERSION

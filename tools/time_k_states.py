@@ -1,6 +1,6 @@
 """Developer tool (GPU box): the K-only launch at S(2236) in the three cache states bench.py quotes
 (back to back / behind 512 MB of unrelated reads / behind 512 MB of unrelated writes), with the
-kernel's non-temporal value stores and with plain stores (ablation build, flag 1024), and with a
+kernel's non-temporal value stores and with plain stores (TFEM_RINGS_STORES), and with a
 pause between the writes and the launch (is it the write-back of the dirty lines that collides?).
 
     python tools/time_k_states.py [n]
