@@ -424,6 +424,32 @@ int tfem_p1_assemble_rings_source(const void *coords, int real_bytes, int64_t n_
                                   void *vals, int64_t nnz, const tfem_source_program *source,
                                   int64_t n_elems, void *fout, void *stream);
 
+/* Variable coefficients: the CSR values of
+ *   alpha * int kappa(x, y) grad u . grad v + beta * int c(x, y) u v
+ * over a ring plan, kappa and c source programs (HOST) evaluated at the integration points inside
+ * the launch (replaces abstract_basis.py:74-93 applied to a caller's `kappa * (v_grad @ v_grad.mT)
+ * + c * (v @ v.mT)`, whose (n_elems, Q, 3, 3) integrand the reference builds with torch).  A NULL
+ * program leaves that term its constant coefficient 1; with BOTH NULL the call fails with
+ * TFEM_ERR_INVALID_ARGUMENT (tfem_p1_assemble_rings is the entry point then).  Both programs are
+ * validated as by tfem_source_validate before anything is launched.  vals (DEVICE): the nnz values
+ * of the CSR pattern the plan was built from; every entry of a row with at least one element is
+ * written exactly once.  The call takes no nnz and the plan's layout carries none: the value stores
+ * are bounds-checked against rows * longest row (layout[1] * layout[5]) reals, an upper bound of
+ * nnz, and that product times real_bytes must stay below 2^32 (TFEM_ERR_INDEX_RANGE otherwise,
+ * somewhat earlier than tfem_p1_assemble_rings would refuse).  No allocation, no synchronisation.  Plans with long rows (layout[23] > 0)
+ * are refused with TFEM_ERR_UNSUPPORTED.  K_ij and K_ji agree to rounding, not bit for bit: a row
+ * visits the integration points of a triangle starting from its own vertex. */
+int tfem_p1_rings_coef(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
+                       double alpha, double beta, const tfem_source_program *kappa,
+                       const tfem_source_program *c, const void *plan_device,
+                       const int64_t *plan_layout_host, void *vals, void *stream);
+/* The same operator applied: y[n_verts] = K u without the CSR values (abstract_basis.py:74-93, applied
+ * instead of stored); u == NULL: y = diag(K).  u and y as for tfem_p1_apply_rings. */
+int tfem_p1_apply_rings_coef(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
+                             double alpha, double beta, const tfem_source_program *kappa,
+                             const tfem_source_program *c, const void *plan_device,
+                             const int64_t *plan_layout_host, const void *u, void *y, void *stream);
+
 /* Multi-GPU: the rows shared with other ranks first.  create_priority = create with
  * vertex_priority_host (n_verts bytes, non-zero = flagged; NULL = none): the tiles that own a flagged
  * vertex come first in the plan's tile list (*n_priority_tiles of them), the order inside both groups

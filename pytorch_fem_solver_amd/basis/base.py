@@ -182,10 +182,20 @@ class AbstractBasis(abc.ABC):
 
         ``layout``: "dense" (the reference's (N, N) tensor), "csr" (``CSRMatrix``), "operator"
         (``FormOperator``: to apply and solve with; matrix-free for ``alpha * v_grad @ v_grad.mT +
-        beta * v @ v.mT`` on a P1 basis with a ring plan, the assembled CSR otherwise) or None =
-        dense while it fits ``DENSE_LIMIT_BYTES``, CSR beyond.
+        beta * v @ v.mT`` on a P1 basis with a ring plan -- also with coefficients ``kappa(x, y)``,
+        ``c(x, y)`` written as expressions of the integration points' columns in front of the two
+        terms -- the assembled CSR otherwise) or None = dense while it fits ``DENSE_LIMIT_BYTES``,
+        CSR beyond.
         """
-        expr = forms.trace(function, self, args, kwargs)
+        return self._bilinear_of(forms.trace(function, self, args, kwargs), layout)
+
+    def _bilinear_of(self, expr, layout):
+        """integrate_bilinear_form for the traced expression (the callable has run)."""
+        if isinstance(expr, forms.BilinearExpr) and expr.has_coefficients:
+            out = self._coefficient_form(expr, layout)
+            if out is not None:
+                return out
+            expr = forms.materialize(expr)  # no launch for it on this basis: the integrand, with torch
         if layout == "operator" and isinstance(expr, forms.BilinearExpr) and self._engine.may_apply_matrix_free():
             # nothing is launched here: the ring plan is built on first use, and a basis whose fans
             # turn out to have no ring form assembles the CSR operator then
@@ -197,15 +207,59 @@ class AbstractBasis(abc.ABC):
         if isinstance(expr, forms.BilinearExpr):
             vals = self._engine.bilinear(expr.alpha, expr.beta)
         else:
-            integrand = forms.materialize(expr)
-            if integrand.requires_grad and torch.is_grad_enabled():
-                raise NotImplementedError(
-                    "integrate_bilinear_form: the integrand carries autograd history, but the "
-                    "assembled operator is written by the HIP kernels and is not differentiable; "
-                    "detach() the integrand, or differentiate a linear form / functional instead"
-                )
-            vals = self._engine.reduce_bilinear(integrand, self._dx)
+            vals = self._reduce_integrand(forms.materialize(expr))
         return self._finish_matrix(vals, layout)
+
+    def _reduce_integrand(self, integrand):
+        """CSR values of a materialised bilinear integrand: the generic reduce + scatter kernels."""
+        if integrand.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(
+                "integrate_bilinear_form: the integrand carries autograd history, but the "
+                "assembled operator is written by the HIP kernels and is not differentiable; "
+                "detach() the integrand, or differentiate a linear form / functional instead"
+            )
+        return self._engine.reduce_bilinear(integrand, self._dx)
+
+    def _coefficient_programs(self, expr):
+        """(kappa, c) source programs of a traced variable-coefficient form, or None when a field
+        does not fit a program (said once per basis) or the basis takes no source programs."""
+        programs = []
+        for field in (expr.kappa, expr.c):
+            program = None
+            if field is not None:
+                program = self._source_program(field)
+                if program is None:
+                    return None
+            programs.append(program)
+        return tuple(programs)
+
+    def _coefficient_form(self, expr, layout):
+        """``alpha * kappa * stiffness + beta * c * mass`` through the coefficient launches
+        (tfem_p1_rings_coef / tfem_p1_apply_rings_coef), or None when they do not apply."""
+        engine, alpha, beta = self._engine, expr.alpha, expr.beta
+        if not (engine.may_apply_matrix_free() and engine.supports_source()):
+            return None
+        if layout == "operator":
+            # nothing is launched and no plan is built here (as for constant coefficients): the operator
+            # decides on first use; without a plan for the launch it assembles the integrand's CSR
+            programs = self._coefficient_programs(expr)
+            if programs is None:
+                return None
+
+            def assemble():
+                vals = engine.bilinear_coef(alpha, beta, *programs)
+                if vals is None:
+                    vals = self._reduce_integrand(forms.materialize(expr))
+                return engine.wrap_csr_home(vals)
+
+            return FormOperator(engine.n_dofs, engine.dtype, engine.home, assemble, engine=engine, alpha=alpha,
+                                beta=beta, programs=programs)
+        if not engine.supports_coefficients():  # builds the ring plan, as an assembly does
+            return None
+        programs = self._coefficient_programs(expr)
+        if programs is None:
+            return None
+        return self._finish_matrix(engine.bilinear_coef(alpha, beta, *programs), layout)
 
     def assemble_system(self, bilinear, linear, *args, layout=None, **kwargs):
         """``(integrate_bilinear_form(bilinear, ...), integrate_linear_form(linear, ...))`` -- the
@@ -217,6 +271,9 @@ class AbstractBasis(abc.ABC):
         a_expr = forms.trace(bilinear, self, args, kwargs)
         l_expr = forms.trace(linear, self, args, kwargs)
         fused = None
+        if isinstance(a_expr, forms.BilinearExpr) and a_expr.has_coefficients:
+            # the coefficient K launch, then the load vector's own launch (two launches)
+            return self._bilinear_of(a_expr, layout), self._linear_of(l_expr)
         if isinstance(a_expr, forms.BilinearExpr) and isinstance(l_expr, forms.LinearExpr) and l_expr.flux is None:
             coefficient = l_expr.coefficient
             if isinstance(coefficient, forms.SourceExpr):
@@ -266,7 +323,10 @@ class AbstractBasis(abc.ABC):
 
     def integrate_linear_form(self, function, *args, **kwargs):
         """Global vector of a linear form, shape (N, 1) (abstract_basis.py:95-112)."""
-        expr = forms.trace(function, self, args, kwargs)
+        return self._linear_of(forms.trace(function, self, args, kwargs))
+
+    def _linear_of(self, expr):
+        """integrate_linear_form for the traced expression (the callable has run)."""
         if isinstance(expr, forms.LinearExpr) and expr.flux is None:
             coefficient = expr.coefficient
             if isinstance(coefficient, forms.SourceExpr):

@@ -1121,6 +1121,90 @@ class AssemblyEngine:
         from the same launch without u."""
         return self._dofs_out(self._apply_rings(alpha, beta, None))
 
+    # ------------------------------------------------------------------ variable coefficients
+    def _coef_rings(self):
+        """The ring plan when the coefficient launches (csrc/tfem_rings_coef.hip) apply: P1 on one
+        mesh with a ring plan (kernel "auto" / "rings") WITHOUT long rows, and a basis that takes
+        source programs.  None otherwise: P2, fractures, batched meshes, every other kernel mode,
+        TFEM_RING_LONG=1 plans -- the form then goes through the materialised integrand."""
+        if not (self.may_apply_matrix_free() and self.supports_source()):
+            return None
+        try:
+            rings = self.ring_plan()
+        except NotImplementedError:
+            return None
+        if rings is None or int(rings["layout"][23]) > 0:
+            return None
+        # the launch addresses the CSR values with 32-bit offsets and bounds them by rows x longest row
+        if int(rings["layout"][1]) * int(rings["layout"][5]) * self.real_bytes >= 1 << 32:
+            return None
+        return rings
+
+    def supports_coefficients(self):
+        return self._coef_rings() is not None
+
+    @staticmethod
+    def _program_ref(program):
+        return ctypes.byref(program) if program is not None else None
+
+    def bilinear_coef(self, alpha, beta, kappa, c, out=None):
+        """CSR values of alpha * int kappa grad u . grad v + beta * int c u v, kappa / c source
+        programs (None: the constant 1) evaluated inside ONE tfem_p1_rings_coef launch; None when
+        the launch does not apply to this basis (the caller materialises the integrand)."""
+        rings = self._coef_rings()
+        if rings is None:
+            return None
+        d = self._inputs()
+        nnz = int(self.csr_structure()[1].shape[0])
+        vals = self._output(out, nnz, "CSR values")
+        with torch.cuda.device(self.device):
+            _native.check(
+                self.lib.tfem_p1_rings_coef(
+                    _native.ptr(d["coords"]), self.real_bytes, self.n_dofs, self.quad_order, float(alpha),
+                    float(beta), self._program_ref(kappa), self._program_ref(c), _native.ptr(rings["blob"]),
+                    c_void_p(rings["layout"].ctypes.data), _native.ptr(vals), self._stream(),
+                )
+            )
+        return vals
+
+    def _apply_rings_coef(self, alpha, beta, kappa, c, u, out=None):
+        """One tfem_p1_apply_rings_coef launch in the ENGINE's numbering: K u of the
+        variable-coefficient form without its CSR values, u None: the diagonal."""
+        rings = self._coef_rings()
+        if rings is None:
+            raise NotImplementedError("the variable-coefficient operator needs a ring plan without long rows (P1)")
+        d = self._inputs()
+        if u is not None:
+            u = u.to(self.device, self.dtype).reshape(-1).contiguous()
+            if u.shape[0] != self.n_dofs:
+                raise ValueError(f"apply: u has {u.shape[0]} entries, the operator {self.n_dofs} columns")
+        y = self._output(out, self.n_dofs, "operator result")
+        if u is not None and y.data_ptr() == u.data_ptr():
+            raise ValueError("apply: out must not be u")
+        with torch.cuda.device(self.device):
+            _native.check(
+                self.lib.tfem_p1_apply_rings_coef(
+                    _native.ptr(d["coords"]), self.real_bytes, self.n_dofs, self.quad_order, float(alpha),
+                    float(beta), self._program_ref(kappa), self._program_ref(c), _native.ptr(rings["blob"]),
+                    c_void_p(rings["layout"].ctypes.data), _native.ptr(u), _native.ptr(y), self._stream(),
+                )
+            )
+        return y
+
+    def apply_coef(self, alpha, beta, kappa, c, u, out=None):
+        """K u of the variable-coefficient form, matrix-free; u and the result (flat, n_dofs) in the
+        caller's numbering (the programs are functions of the coordinates and need no translation)."""
+        if self._perm is None:
+            return self._apply_rings_coef(alpha, beta, kappa, c, u, out)
+        y = self._dofs_out(self._apply_rings_coef(alpha, beta, kappa, c, self._dofs_in(u.to(self.device).reshape(-1))))
+        if out is not None:
+            return self._output(out, self.n_dofs, "operator result").copy_(y)
+        return y
+
+    def operator_diagonal_coef(self, alpha, beta, kappa, c):
+        """diag(K) of the variable-coefficient form in the caller's numbering."""
+        return self._dofs_out(self._apply_rings_coef(alpha, beta, kappa, c, None))
+
     def prepared_system(self, alpha, beta, out, fq=None, source=None, tiles=None):
         """The launch of assemble_system(alpha, beta, fq | source, out=out, tiles=tiles) with every
         argument converted ONCE: the returned callable only enqueues on the current stream

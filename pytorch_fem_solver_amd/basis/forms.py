@@ -7,6 +7,9 @@ The user's callable is called ONCE with a proxy basis whose ``v``, ``v_grad`` an
     v_grad @ v_grad.mT            (stiffness)       examples/example_fractures_fem.py:112-116
     v @ v.mT                      (mass)
     c1 * stiffness + c2 * mass    (python scalars)  tests/test_assembly.py:68-73
+    kappa * stiffness + c * mass  (kappa, c expressions of the coordinate columns as below: the
+                                  variable coefficients of -div(kappa grad u) + c u; P1 launches
+                                  evaluate them per triangle, csrc/tfem_rings_coef.hip)
     f * v   /   v * f             f a tensor broadcastable to (..., Q, 1, 1), or an
                                   expression of the coordinate columns of
                                   ``integration_points`` (``torch.split(points, 1, dim=-1)``,
@@ -168,45 +171,115 @@ class ShapeGradients(_Symbol):
         return super().__matmul__(other)
 
 
-class BilinearExpr(_Symbol):
-    """alpha * (v_grad @ v_grad.mT) + beta * (v @ v.mT)"""
+def _scaled_node(node, factor):
+    """The node of ``factor * field`` (a python scalar times a coefficient's node)."""
+    if factor == 1.0:
+        return node
+    if node[0] == "c":
+        return ("c", factor * node[1])
+    return ("mul", ("c", factor), node)
 
-    def __init__(self, basis, alpha, beta):
+
+class BilinearExpr(_Symbol):
+    """alpha * kappa(x, y) * (v_grad @ v_grad.mT) + beta * c(x, y) * (v @ v.mT)
+
+    ``alpha`` / ``beta``: python scalars; ``kappa`` / ``c``: None (the constant 1) or a SourceExpr
+    of the coordinate columns -- the variable coefficients of -div(kappa grad u) + c u."""
+
+    def __init__(self, basis, alpha, beta, kappa=None, c=None):
         super().__init__(basis)
         object.__setattr__(self, "alpha", float(alpha))
         object.__setattr__(self, "beta", float(beta))
+        object.__setattr__(self, "kappa", kappa)
+        object.__setattr__(self, "c", c)
+
+    @property
+    def has_coefficients(self):
+        return self.kappa is not None or self.c is not None
 
     def materialize(self):
+        # the caller's operations on the real tensors: coefficient * form, scalar factor outside
         b = self._basis
         out = None
         if self.alpha != 0.0:
-            out = self.alpha * (b.v_grad @ b.v_grad.mT) if self.alpha != 1.0 else b.v_grad @ b.v_grad.mT
+            out = b.v_grad @ b.v_grad.mT
+            if self.kappa is not None:
+                out = materialize(self.kappa) * out
+            if self.alpha != 1.0:
+                out = self.alpha * out
         if self.beta != 0.0:
-            m = self.beta * (b.v @ b.v.mT) if self.beta != 1.0 else b.v @ b.v.mT
+            m = b.v @ b.v.mT
+            if self.c is not None:
+                m = materialize(self.c) * m
+            if self.beta != 1.0:
+                m = self.beta * m
             out = m if out is None else out + m
         return out if out is not None else 0.0 * (b.v @ b.v.mT)
 
+    # ---- sums: scalar factors add; coefficients of the same term add as fields -------------
+    @staticmethod
+    def _term(basis, f1, s1, f2, s2):
+        """(factor, field) of f1 * s1 + f2 * s2, s1 / s2 a SourceExpr or None (= 1)."""
+        if s1 is None and s2 is None:
+            return f1 + f2, None
+        if f2 == 0.0:
+            return f1, s1
+        if f1 == 0.0:
+            return f2, s2
+        n1 = _scaled_node(s1.node, f1) if s1 is not None else ("c", f1)
+        n2 = _scaled_node(s2.node, f2) if s2 is not None else ("c", f2)
+        return 1.0, SourceExpr(basis, ("add", n1, n2))
+
+    def _sum(self, other, sign):
+        alpha, kappa = self._term(self._basis, self.alpha, self.kappa, sign * other.alpha, other.kappa)
+        beta, c = self._term(self._basis, self.beta, self.c, sign * other.beta, other.c)
+        return BilinearExpr(self._basis, alpha, beta, kappa, c)
+
     def __add__(self, other):
         if isinstance(other, BilinearExpr):
-            return BilinearExpr(self._basis, self.alpha + other.alpha, self.beta + other.beta)
+            return self._sum(other, 1.0)
         return super().__add__(other)
 
     __radd__ = __add__
 
     def __sub__(self, other):
         if isinstance(other, BilinearExpr):
-            return BilinearExpr(self._basis, self.alpha - other.alpha, self.beta - other.beta)
+            return self._sum(other, -1.0)
         return super().__sub__(other)
+
+    # ---- products with a scalar or with a scalar field of the coordinates --------------------
+    def _times_field(self, field):
+        """field * self for a PURE term (stiffness only or mass only), else None."""
+        if field.node[0] == "c":  # a constant written as a field: a scalar factor
+            return BilinearExpr(self._basis, self.alpha * field.node[1], self.beta * field.node[1], self.kappa, self.c)
+        if self.alpha != 0.0 and self.beta == 0.0 and self.c is None:
+            kappa = field if self.kappa is None else SourceExpr(self._basis, ("mul", self.kappa.node, field.node))
+            return BilinearExpr(self._basis, self.alpha, 0.0, kappa, None)
+        if self.beta != 0.0 and self.alpha == 0.0 and self.kappa is None:
+            c = field if self.c is None else SourceExpr(self._basis, ("mul", self.c.node, field.node))
+            return BilinearExpr(self._basis, 0.0, self.beta, None, c)
+        return None
 
     def __mul__(self, other):
         if _is_scalar(other):
-            return BilinearExpr(self._basis, self.alpha * _scalar(other), self.beta * _scalar(other))
+            return BilinearExpr(self._basis, self.alpha * _scalar(other), self.beta * _scalar(other), self.kappa, self.c)
+        if isinstance(other, SourceExpr):
+            out = self._times_field(other)
+            if out is not None:
+                return out
         return super().__mul__(other)
 
     __rmul__ = __mul__
 
+    def __truediv__(self, other):
+        if isinstance(other, SourceExpr):
+            out = self._times_field(SourceExpr(self._basis, ("c", 1.0)).__truediv__(other))
+            if out is not None:
+                return out
+        return super().__truediv__(other)
+
     def __neg__(self):
-        return BilinearExpr(self._basis, -self.alpha, -self.beta)
+        return BilinearExpr(self._basis, -self.alpha, -self.beta, self.kappa, self.c)
 
 
 class LinearExpr(_Symbol):
@@ -364,13 +437,13 @@ class SourceExpr(_Symbol):
         return out if out is not None else super().__rsub__(other)
 
     def __mul__(self, other):
-        if isinstance(other, ShapeFunctions):
+        if isinstance(other, (ShapeFunctions, BilinearExpr)):
             return other.__mul__(self)
         out = self._arith(other, "mul")
         return out if out is not None else super().__mul__(other)
 
     def __rmul__(self, other):
-        if isinstance(other, ShapeFunctions):
+        if isinstance(other, (ShapeFunctions, BilinearExpr)):
             return other.__mul__(self)
         out = self._arith(other, "mul", True)
         return out if out is not None else super().__rmul__(other)

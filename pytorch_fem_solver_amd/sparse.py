@@ -221,18 +221,23 @@ class FormOperator:
 
     Matrix-free (``matrix_free`` True): ``alpha * stiffness + beta * mass`` of a P1 basis whose
     engine has a ring plan; every ``matvec`` is one tfem_p1_apply_rings launch that forms the rows
-    of K in registers and writes K u -- the values of K are never stored.  Otherwise the operator
+    of K in registers and writes K u -- the values of K are never stored.  The operator may carry
+    the source programs of variable coefficients kappa(x, y), c(x, y) (tfem_p1_apply_rings_coef then:
+    the programs are evaluated per triangle inside the launch).  Otherwise the operator
     wraps the CSRMatrix of today's assembly and applies it with tfem_csr_spmv (P2, fractures, any
     other integrand, meshes without a ring plan); the interface and the results are the same.
     Vectors are taken and returned in the caller's DoF numbering, of shape (N,) or (N, 1)."""
 
-    def __init__(self, n, dtype, device, assemble, engine=None, alpha=0.0, beta=0.0, symmetric=True):
+    def __init__(self, n, dtype, device, assemble, engine=None, alpha=0.0, beta=0.0, symmetric=True,
+                 programs=None):
         self.shape = (int(n), int(n))
         self.dtype = dtype
         self.device = device
         self._assemble = assemble  # () -> CSRMatrix on `device`: the assembled form
         self._engine = engine      # None: the CSR path only
         self.alpha, self.beta = float(alpha), float(beta)
+        #: (kappa, c) source programs of a variable-coefficient form (None: constant coefficients)
+        self._programs = programs
         self._symmetric = symmetric
         self._csr = None
         self._matrix_free = None if engine is not None else False
@@ -246,10 +251,19 @@ class FormOperator:
         """Decided on first use: the ring plan is built then (as for an assembly), not before."""
         if self._matrix_free is None:
             try:
-                self._matrix_free = self._engine.ring_plan() is not None
+                if self._programs is not None:
+                    self._matrix_free = self._engine.supports_coefficients()
+                else:
+                    self._matrix_free = self._engine.ring_plan() is not None
             except NotImplementedError:
                 self._matrix_free = False
         return self._matrix_free
+
+    def _rows(self, u):
+        """K u (u None: diag K) by one launch in the engine's numbering."""
+        if self._programs is not None:
+            return self._engine._apply_rings_coef(self.alpha, self.beta, *self._programs, u)
+        return self._engine._apply_rings(self.alpha, self.beta, u)
 
     def to_csr(self):
         """The assembled operator (CSRMatrix) through the existing assembly path (cached)."""
@@ -267,7 +281,10 @@ class FormOperator:
         flat = self._check(x)
         if self.matrix_free:
             engine = self._engine
-            y = engine._home(engine.apply(self.alpha, self.beta, flat))
+            if self._programs is not None:
+                y = engine._home(engine.apply_coef(self.alpha, self.beta, *self._programs, flat))
+            else:
+                y = engine._home(engine.apply(self.alpha, self.beta, flat))
         else:
             y = self.to_csr().matvec(flat.to(self.device))
         return y.reshape(x.shape)
@@ -287,6 +304,8 @@ class FormOperator:
         """diag(K), shape (N,)."""
         if self.matrix_free:
             engine = self._engine
+            if self._programs is not None:
+                return engine._home(engine.operator_diagonal_coef(self.alpha, self.beta, *self._programs))
             return engine._home(engine.operator_diagonal(self.alpha, self.beta))
         return self.to_csr().diagonal()
 
@@ -309,11 +328,13 @@ class FormOperator:
             if inv is not None:
                 free_e = inv[free_e]
         x, it, res = conjugate_gradients(
-            lambda p: engine._apply_rings(self.alpha, self.beta, p), engine._apply_rings(self.alpha, self.beta, None),
+            self._rows, self._rows(None),
             inward(b), free_e, inward(x0), rtol, maxiter,
         )
         return engine._home(engine._dofs_out(x)).reshape(b.shape), it, res
 
     def __repr__(self):
         kind = "matrix-free" if self._matrix_free else ("CSR" if self._matrix_free is False else "unresolved")
+        if self._programs is not None and self._matrix_free is not False:
+            kind = "matrix-free, variable coefficients" if self._matrix_free else "unresolved, variable coefficients"
         return f"FormOperator(shape={self.shape}, dtype={self.dtype}, device={self.device}, {kind})"

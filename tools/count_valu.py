@@ -1,5 +1,6 @@
 """A few launches of every variant of the P1 launch, for `rocprofv3 --pmc SQ_INSTS_VALU ...`:
-which variant issues how many vector instructions (tools/count_valu.sh summarises)."""
+which variant issues how many vector instructions (tools/count_valu.sh summarises; the
+coefficient launches of two programs share a kernel name: the summary gives mean, min and max)."""
 import math
 import os
 import sys
@@ -37,4 +38,14 @@ for _ in range(8):
     eng.assemble_system(1.0, 0.0, source=poly)
 for _ in range(9):
     eng.assemble_system(1.0, 0.0, source=program)
+# the variable-coefficient launches (k_p1_coef_rows: store and apply mode), one program after the other:
+# kappa = 1 + x y (10 and 11 launches), kappa = 1 + 0.5 sin(3x) cos(2y) (12 and 13)
+trig = forms.compile_program(("add", ("c", 1.0), ("mul", ("mul", ("c", 0.5), ("sin", ("mul", ("c", 3.0), ("x",)))),
+                                                  ("cos", ("mul", ("c", 2.0), ("y",))))))
+u = torch.rand(eng.n_dofs)
+for count, kappa in ((10, poly), (12, trig)):
+    for _ in range(count):
+        eng.bilinear_coef(1.0, 0.0, kappa, None)
+    for _ in range(count + 1):
+        eng._apply_rings_coef(1.0, 0.0, kappa, None, u)
 torch.cuda.synchronize()

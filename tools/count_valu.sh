@@ -9,10 +9,13 @@ import csv, glob, collections
 rows = collections.defaultdict(lambda: collections.defaultdict(list))
 for path in glob.glob("$OUT/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(path)):
-        if "k_p1_rings" in r["Kernel_Name"]:
+        if "k_p1_rings" in r["Kernel_Name"] or "k_p1_coef_rows" in r["Kernel_Name"]:
             rows[r["Kernel_Name"]][r["Counter_Name"]].append(float(r["Counter_Value"]))
 for name, cs in rows.items():
     n = len(next(iter(cs.values())))
     print(n, name.split("(")[0])
     print("    " + "  ".join(f"{c}={sum(v)/len(v):.4g}" for c, v in sorted(cs.items())))
+    if "k_p1_coef_rows" in name:
+        v = cs["SQ_INSTS_VALU"]
+        print(f"    SQ_INSTS_VALU min {min(v):.4g} max {max(v):.4g}")
 PY
