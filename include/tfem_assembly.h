@@ -359,6 +359,17 @@ int tfem_p1_assemble_rings(const void *coords, int real_bytes, int64_t n_verts, 
 int tfem_p1_apply_rings(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
                         double alpha, double beta, const void *plan_device,
                         const int64_t *plan_layout_host, const void *u, void *y, void *stream);
+/* Y = (alpha * stiffness + beta * mass) U for n_vec vectors at once: U and Y (DEVICE, n_verts x n_vec
+ * reals each, ROW-major: the n_vec values of a vertex are consecutive; the plan's vertex numbering)
+ * must not overlap; every entry of Y is written once.  The rows of K are formed once per pass of up
+ * to 8 columns (as many as the plan's tiles hold in 64 KB of LDS), a larger n_vec is served in
+ * several passes over column ranges.  n_vec >= 1 of any size within the 32-bit extent (n_vec = 1
+ * gives what tfem_p1_apply_rings gives); u == NULL is an error here (the diagonal has one column:
+ * tfem_p1_apply_rings).  No allocation, no synchronisation. */
+int tfem_p1_apply_rings_multi(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
+                              double alpha, double beta, const void *plan_device,
+                              const int64_t *plan_layout_host, const void *u, void *y,
+                              int64_t n_vec, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Source programs: the coefficient f of the linear form f(x_q) * v

@@ -404,11 +404,16 @@ class AbstractBasis(abc.ABC):
         DENSE_SOLVE_LIMIT rows (or method="cg") is solved by Jacobi-preconditioned conjugate
         gradients on the CSR values (CSRMatrix.solve_cg; symmetric positive definite forms):
         the step after the assembly for operators the reference cannot hold.
-        A FormOperator (layout="operator") is always solved by CG, matrix-free where it is."""
+        A FormOperator (layout="operator") is always solved by CG, matrix-free where it is.
+        With ``solution`` and ``vector`` of shape (N, k), k >= 2, the CG path solves the k systems
+        together (``solve_cg_multi``)."""
         if isinstance(matrix, FormOperator) or (
                 isinstance(matrix, CSRMatrix) and (method == "cg" or (method is None and matrix.shape[0] > self.DENSE_SOLVE_LIMIT))):
             free = self._basis_parameters["inner_dofs"] if only_inner_dofs is True else None
-            x, _, _ = matrix.solve_cg(vector, free=free)
+            if vector.dim() == 2 and vector.shape[1] > 1:  # (N, k): the k systems in one block CG
+                x, _, _ = matrix.solve_cg_multi(vector, free=free)
+            else:
+                x, _, _ = matrix.solve_cg(vector, free=free)
             if free is None:
                 solution += x.reshape(solution.shape).to(solution.device)
             else:

@@ -23,6 +23,11 @@ class NoDeviceError(RuntimeError):
     pass
 
 
+def _is_block(u):
+    """A block of k >= 2 vectors, shape (N, k) ((N,) and (N, 1) are single vectors)."""
+    return u is not None and u.dim() == 2 and u.shape[1] > 1
+
+
 def _compute_device(home: torch.device) -> torch.device:
     if home.type == "cuda":
         return home
@@ -456,6 +461,8 @@ class AssemblyEngine:
         """A per-DoF vector of the engine -> the caller's numbering."""
         if self._perm is None or vec is None:
             return vec
+        if _is_block(vec):  # (N, k): the renumbering acts on rows
+            return vec.index_select(0, self._inv.to(vec.device))
         flat = vec.reshape(-1)
         return flat.index_select(0, self._inv.to(flat.device)).reshape(vec.shape)
 
@@ -463,6 +470,8 @@ class AssemblyEngine:
         """A per-DoF vector of the caller -> the engine's numbering."""
         if self._perm is None or vec is None:
             return vec
+        if _is_block(vec):
+            return vec.index_select(0, self._perm.to(vec.device))
         flat = vec.reshape(-1)
         return flat.index_select(0, self._perm.to(flat.device)).reshape(vec.shape)
 
@@ -1085,6 +1094,8 @@ class AssemblyEngine:
         """One tfem_p1_apply_rings launch in the ENGINE's numbering: (alpha * stiffness + beta *
         mass) u without the CSR values, u None: the diagonal.  Launches over the ring plan
         whenever it exists, whatever _use_rings() prefers for the assembly."""
+        if _is_block(u):
+            return self._apply_rings_multi(alpha, beta, u, out)
         rings = self.ring_plan()
         if rings is None:
             raise NotImplementedError("the matrix-free operator needs the ring plan (P1, fans with a ring form)")
@@ -1106,11 +1117,41 @@ class AssemblyEngine:
             )
         return y
 
+    def _apply_rings_multi(self, alpha, beta, u, out=None):
+        """One tfem_p1_apply_rings_multi call in the ENGINE's numbering: K U for U of shape
+        (n_dofs, k), k >= 2, every row of K formed once per pass of columns.  Returns (n_dofs, k)."""
+        rings = self.ring_plan()
+        if rings is None:
+            raise NotImplementedError("the matrix-free operator needs the ring plan (P1, fans with a ring form)")
+        d = self._inputs()
+        u = u.to(self.device, self.dtype).contiguous()  # row-major: a vertex's k values are consecutive
+        if u.shape[0] != self.n_dofs:
+            raise ValueError(f"apply: u has {u.shape[0]} rows, the operator {self.n_dofs} columns")
+        k = int(u.shape[1])
+        y = self._output(out, self.n_dofs * k, "operator result")
+        if y.data_ptr() == u.data_ptr():
+            raise ValueError("apply: out must not be u")
+        with torch.cuda.device(self.device):
+            _native.check(
+                self.lib.tfem_p1_apply_rings_multi(
+                    _native.ptr(d["coords"]), self.real_bytes, self.n_dofs, self.quad_order, float(alpha),
+                    float(beta), _native.ptr(rings["blob"]), c_void_p(rings["layout"].ctypes.data),
+                    _native.ptr(u), _native.ptr(y), k, self._stream(),
+                )
+            )
+        return y.view(self.n_dofs, k)
+
     def apply(self, alpha, beta, u, out=None):
         """(alpha * stiffness + beta * mass) u, matrix-free over the ring plan; u and the result
-        (flat, n_dofs) in the caller's numbering.  ``out``: a preallocated device buffer."""
+        (flat, n_dofs) in the caller's numbering, or (n_dofs, k) for k >= 2 vectors in one launch.
+        ``out``: a preallocated device buffer."""
         if self._perm is None:
             return self._apply_rings(alpha, beta, u, out)
+        if _is_block(u):
+            y = self._dofs_out(self._apply_rings_multi(alpha, beta, self._dofs_in(u.to(self.device))))
+            if out is not None:
+                return self._output(out, y.numel(), "operator result").copy_(y.reshape(-1)).view(y.shape)
+            return y
         y = self._dofs_out(self._apply_rings(alpha, beta, self._dofs_in(u.to(self.device).reshape(-1))))
         if out is not None:
             return self._output(out, self.n_dofs, "operator result").copy_(y)
@@ -1170,6 +1211,13 @@ class AssemblyEngine:
     def _apply_rings_coef(self, alpha, beta, kappa, c, u, out=None):
         """One tfem_p1_apply_rings_coef launch in the ENGINE's numbering: K u of the
         variable-coefficient form without its CSR values, u None: the diagonal."""
+        if _is_block(u):  # one launch per column (a multi-column coefficient kernel: DESIGN.md section 7)
+            u = u.to(self.device, self.dtype)
+            cols = [self._apply_rings_coef(alpha, beta, kappa, c, u[:, j]) for j in range(u.shape[1])]
+            y = torch.stack(cols, dim=1)
+            if out is not None:
+                return self._output(out, y.numel(), "operator result").copy_(y.reshape(-1)).view(y.shape)
+            return y
         rings = self._coef_rings()
         if rings is None:
             raise NotImplementedError("the variable-coefficient operator needs a ring plan without long rows (P1)")
@@ -1196,6 +1244,11 @@ class AssemblyEngine:
         caller's numbering (the programs are functions of the coordinates and need no translation)."""
         if self._perm is None:
             return self._apply_rings_coef(alpha, beta, kappa, c, u, out)
+        if _is_block(u):
+            y = self._dofs_out(self._apply_rings_coef(alpha, beta, kappa, c, self._dofs_in(u.to(self.device))))
+            if out is not None:
+                return self._output(out, y.numel(), "operator result").copy_(y.reshape(-1)).view(y.shape)
+            return y
         y = self._dofs_out(self._apply_rings_coef(alpha, beta, kappa, c, self._dofs_in(u.to(self.device).reshape(-1))))
         if out is not None:
             return self._output(out, self.n_dofs, "operator result").copy_(y)

@@ -107,7 +107,12 @@ class CSRMatrix:
         return dense
 
     def matvec(self, x):
-        """A @ x for x of shape (N,) or (N, 1): libtfem_hip's CSR kernel on the GPU."""
+        """A @ x for x of shape (N,) or (N, 1): libtfem_hip's CSR kernel on the GPU.  (N, k) with
+        k >= 2: the same launch once per column, result (N, k)."""
+        if _is_block(x):
+            if x.shape[0] != self.shape[1]:
+                raise ValueError(f"matvec: x has {x.shape[0]} rows, the operator {self.shape[1]} columns")
+            return torch.stack([self.matvec(x[:, j]) for j in range(x.shape[1])], dim=1)
         if self.perm is not None:
             flat = x.to(self.device, self.dtype).reshape(-1)
             return self._stored().matvec(flat[self.perm])[self._inverse()].reshape(x.shape)
@@ -156,6 +161,17 @@ class CSRMatrix:
         x, it, res = conjugate_gradients(self.matvec, self.diagonal(), b, free, x0, rtol, maxiter)
         return x.reshape(b.shape), it, res
 
+    def solve_cg_multi(self, B, free=None, X0=None, rtol=1e-12, maxiter=None):
+        """``solve_cg`` for the k columns of B (N, k) at once (``conjugate_gradients_multi``): one
+        block application per iteration.  Returns (X (N, k), iterations (k,), relative residuals (k,))."""
+        if self.perm is not None:  # solve in the stored numbering, rows translated at the boundary
+            inv = self._inverse()
+            to_stored = lambda v: None if v is None else v.to(self.device, self.dtype)[self.perm]  # noqa: E731
+            free_s = None if free is None else inv[free.to(self.device).reshape(-1)]
+            X, it, res = self._stored().solve_cg_multi(to_stored(B), free_s, to_stored(X0), rtol, maxiter)
+            return X[inv], it, res
+        return conjugate_gradients_multi(self.matvec, self.diagonal(), B, free, X0, rtol, maxiter)
+
     def __repr__(self):
         extra = "" if self.perm is None else ", stored in a renumbering of the DoFs"
         return f"CSRMatrix(shape={self.shape}, nnz={self.nnz}, dtype={self.dtype}, device={self.device}{extra})"
@@ -200,6 +216,70 @@ def conjugate_gradients(matvec, diagonal, b, free=None, x0=None, rtol=1e-12, max
     return x, it, res
 
 
+def conjugate_gradients_multi(matvec, diagonal, B, free=None, X0=None, rtol=1e-12, maxiter=None):
+    """``conjugate_gradients`` for the k columns of ``B`` (N, k) at once: k independent
+    Jacobi-preconditioned CG recurrences carried through the same tensor operations -- one block
+    application ``matvec`` ((N, k) -> (N, k)) per iteration, column-wise dot products, one alpha
+    and one beta per column.  A column is converged when its relative residual is <= rtol at a
+    check (every 25 iterations, as in ``conjugate_gradients``; a column that starts converged, e.g.
+    an all-zero right-hand side, takes no iteration); from then on it is frozen -- its alpha and
+    beta are zero and its search direction is zeroed, so x, r and p stop changing and no 0/0
+    arises -- and the loop ends when every column is.  Returns (X (N, k), iterations (k,) int64,
+    relative residuals (k,)), the last two on the host."""
+    n = diagonal.shape[0]
+    dtype, device = diagonal.dtype, diagonal.device
+    B = B.to(device, dtype)
+    if B.dim() != 2 or B.shape[0] != n:
+        raise ValueError(f"conjugate_gradients_multi: B must have shape ({n}, k)")
+    k = B.shape[1]
+    mask = torch.ones(n, 1, dtype=dtype, device=device)
+    if free is not None:
+        mask.zero_()
+        mask[free.to(device).reshape(-1)] = 1
+    X = torch.zeros(n, k, dtype=dtype, device=device) if X0 is None else X0.to(device, dtype).reshape(n, k).clone()
+    diag = diagonal.reshape(n, 1)
+    inv_diag = mask / torch.where(diag != 0, diag, torch.ones_like(diag))
+    R = mask * (B - matvec(X))
+    Z = inv_diag * R
+    P = Z.clone()
+    rz = (R * Z).sum(0)
+    b_norm = torch.linalg.vector_norm(mask * B, dim=0).clamp_min(torch.finfo(dtype).tiny)
+    maxiter = maxiter or 10 * n
+    res = torch.linalg.vector_norm(R, dim=0) / b_norm
+    active = res > rtol  # (k,) on the device; its host copy decides the loop
+    P = P * active
+    running = active.cpu()
+    its = torch.zeros(k, dtype=torch.int64)
+    it = 0
+    one = torch.ones((), dtype=dtype, device=device)
+    while it < maxiter and bool(running.any()):
+        AP = mask * matvec(P)
+        pap = (P * AP).sum(0)
+        alpha = torch.where(active, rz / torch.where(active, pap, one), torch.zeros_like(rz))
+        X += alpha * P
+        R -= alpha * AP
+        Z = inv_diag * R
+        rz_new = (R * Z).sum(0)
+        beta = torch.where(active, rz_new / torch.where(active, rz, one), torch.zeros_like(rz))
+        P = torch.where(active, Z + beta * P, P)
+        rz = torch.where(active, rz_new, rz)
+        it += 1
+        if it % 25 == 0 or it == maxiter:  # one host synchronisation every 25 iterations
+            res = torch.linalg.vector_norm(R, dim=0) / b_norm
+            its[running] = it
+            active = active & (res > rtol)
+            P = P * active
+            running = active.cpu()
+    its[running] = it
+    res = torch.linalg.vector_norm(R, dim=0) / b_norm
+    return X, its, res.cpu()
+
+
+def _is_block(x):
+    """A block of k >= 2 vectors, shape (N, k) ((N,) and (N, 1) are single vectors)."""
+    return x.dim() == 2 and x.shape[1] > 1
+
+
 class _OperatorApply(torch.autograd.Function):
     """u -> K u of a symmetric operator, differentiable in u: the backward is the same
     application (K^T = K), e.g. for energy-norm losses u^T K u."""
@@ -226,7 +306,10 @@ class FormOperator:
     the programs are evaluated per triangle inside the launch).  Otherwise the operator
     wraps the CSRMatrix of today's assembly and applies it with tfem_csr_spmv (P2, fractures, any
     other integrand, meshes without a ring plan); the interface and the results are the same.
-    Vectors are taken and returned in the caller's DoF numbering, of shape (N,) or (N, 1)."""
+    Vectors are taken and returned in the caller's DoF numbering, of shape (N,) or (N, 1); a block
+    (N, k) of k >= 2 vectors gives (N, k): matrix-free with constant coefficients by ONE
+    tfem_p1_apply_rings_multi call that forms the rows of K once for the k columns, every other
+    operator by its single-vector launch once per column."""
 
     def __init__(self, n, dtype, device, assemble, engine=None, alpha=0.0, beta=0.0, symmetric=True,
                  programs=None):
@@ -272,6 +355,10 @@ class FormOperator:
         return self._csr
 
     def _check(self, x):
+        if _is_block(x):
+            if x.shape[0] != self.shape[1]:
+                raise ValueError(f"matvec: x has {x.shape[0]} rows, the operator {self.shape[1]} columns")
+            return x
         flat = x.reshape(-1)
         if flat.shape[0] != self.shape[1]:
             raise ValueError(f"matvec: x has {flat.shape[0]} entries, the operator {self.shape[1]} columns")
@@ -290,7 +377,7 @@ class FormOperator:
         return y.reshape(x.shape)
 
     def matvec(self, x):
-        """K x for x of shape (N,) or (N, 1); differentiable in x for symmetric forms."""
+        """K x for x of shape (N,), (N, 1) or (N, k); differentiable in x for symmetric forms."""
         if x.requires_grad and torch.is_grad_enabled():
             if not self._symmetric:
                 raise NotImplementedError("matvec: the gradient needs the transpose of a non-symmetric form")
@@ -332,6 +419,34 @@ class FormOperator:
             inward(b), free_e, inward(x0), rtol, maxiter,
         )
         return engine._home(engine._dofs_out(x)).reshape(b.shape), it, res
+
+    def solve_cg_multi(self, B, free=None, X0=None, rtol=1e-12, maxiter=None):
+        """``solve_cg`` for the k columns of B (N, k) at once: one block apply per iteration
+        (``conjugate_gradients_multi``), in the engine's numbering when matrix-free.  Returns
+        (X (N, k), iterations (k,), relative residuals (k,))."""
+        if not self.matrix_free:
+            return self.to_csr().solve_cg_multi(B, free, X0, rtol, maxiter)
+        engine = self._engine
+        dev, dtype = engine.device, engine.dtype
+        inv = None if engine._inv is None else engine._inv.to(dev)
+
+        def inward(v):
+            if v is None:
+                return None
+            v = v.to(dev, dtype)
+            return v if inv is None else v.index_select(0, engine._perm.to(dev))
+
+        free_e = None
+        if free is not None:
+            free_e = free.to(dev).reshape(-1)
+            if inv is not None:
+                free_e = inv[free_e]
+        X, it, res = conjugate_gradients_multi(
+            self._rows, self._rows(None), inward(B), free_e, inward(X0), rtol, maxiter,
+        )
+        if inv is not None:
+            X = X.index_select(0, inv)
+        return engine._home(X), it, res
 
     def __repr__(self):
         kind = "matrix-free" if self._matrix_free else ("CSR" if self._matrix_free is False else "unresolved")
