@@ -552,6 +552,24 @@ int tfem_p2_assemble_rows(const void *coords, int real_bytes, int quad_order, do
 int tfem_p2_load_rows(const void *coords, int real_bytes, int quad_order, const void *plan_device,
                       const int64_t *plan_layout_host, const void *fq, int64_t n_elems, void *out,
                       int64_t n_dofs, void *stream);
+/* y[n_dofs] = (alpha * stiffness + beta * mass) u for ElementTri(2, .) over the same plan, without
+ * the CSR values (abstract_basis.py:74-93 with element_tri.py:43-70: the operator the reference
+ * assembles, applied instead of stored).  The rows are formed as tfem_p2_assemble_rows forms them;
+ * every entry is multiplied by u of its column and the row's sum is written: one number per DoF,
+ * every entry of y written once (0 for a vertex without elements).  The plan's records hold CSR
+ * positions, so the launch reads colind (nnz int32, the pattern the plan was created from) for the
+ * columns; the row starts come from the plan's descriptors and records, rowptr is not an argument.
+ * u and y (n_dofs reals each, the plan's DoF numbering) must not overlap.  u == NULL: y = diag(K)
+ * (colind is not read then, but is still required).  All pointers DEVICE except plan_layout_host.
+ * Launches: vertex rows, long vertex rows if any, edge rows.  No allocation, no synchronisation.
+ * TFEM_ERR_INVALID_ARGUMENT: real_bytes not 4 or 8, NULL plan_layout_host, negative sizes, n_dofs
+ * != layout[2] + layout[3], u overlapping y, a NULL array or capacities beyond the kernels' on a
+ * non-empty plan; TFEM_ERR_INDEX_RANGE: an array of 4 GiB or more; TFEM_ERR_UNSUPPORTED: an unknown
+ * quadrature order.  Nothing is launched after a refusal. */
+int tfem_p2_apply_rows(const void *coords, int real_bytes, int quad_order, double alpha, double beta,
+                       const void *plan_device, const int64_t *plan_layout_host,
+                       const int32_t *colind, int64_t nnz, const void *u, void *y, int64_t n_dofs,
+                       void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Interface exchange of the multi-GPU sharding (DEVICE; the path shards by element

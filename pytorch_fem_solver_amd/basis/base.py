@@ -184,13 +184,17 @@ class AbstractBasis(abc.ABC):
         (``FormOperator``: to apply and solve with; matrix-free for ``alpha * v_grad @ v_grad.mT +
         beta * v @ v.mT`` on a P1 basis with a ring plan -- also with coefficients ``kappa(x, y)``,
         ``c(x, y)`` written as expressions of the integration points' columns in front of the two
-        terms -- the assembled CSR otherwise) or None = dense while it fits ``DENSE_LIMIT_BYTES``,
-        CSR beyond.
+        terms -- the assembled CSR otherwise), "matrix_free" (a ``FormOperator`` that never stores K,
+        decided here: what "operator" serves matrix-free on P1, and the same form on a P2 basis over
+        its row plan; NotImplementedError naming the reason where no such launch applies) or None =
+        dense while it fits ``DENSE_LIMIT_BYTES``, CSR beyond.
         """
         return self._bilinear_of(forms.trace(function, self, args, kwargs), layout)
 
     def _bilinear_of(self, expr, layout):
         """integrate_bilinear_form for the traced expression (the callable has run)."""
+        if layout == "matrix_free":
+            return self._matrix_free_operator(expr)
         if isinstance(expr, forms.BilinearExpr) and expr.has_coefficients:
             out = self._coefficient_form(expr, layout)
             if out is not None:
@@ -209,6 +213,60 @@ class AbstractBasis(abc.ABC):
         else:
             vals = self._reduce_integrand(forms.materialize(expr))
         return self._finish_matrix(vals, layout)
+
+    def _matrix_free_operator(self, expr):
+        """layout="matrix_free": a FormOperator that never stores K -- the plan is built here -- or
+        NotImplementedError saying why this form on this basis has no such launch."""
+        def refuse(why):
+            raise NotImplementedError(f'layout="matrix_free": {why}')
+
+        engine = self._engine
+        if engine.n_fractures > 0 or engine._host_conn_geo.dim() != 2:
+            refuse("a fracture basis (batched meshes) has no row plan")
+        if not isinstance(expr, forms.BilinearExpr):
+            refuse("the integrand is not alpha * v_grad @ v_grad.mT + beta * v @ v.mT (with coefficient "
+                   "expressions of the integration points in front of the terms on P1)")
+        if engine.poly_order not in (1, 2):
+            refuse(f"no row plan for polynomial order {engine.poly_order}")
+        alpha, beta = expr.alpha, expr.beta
+        if engine.poly_order == 2:
+            if expr.has_coefficients:
+                refuse("coefficient fields on a P2 basis (the P2 row launch takes constant coefficients)")
+            if not engine.may_apply_p2_matrix_free():
+                refuse(f"TFEM_KERNEL={engine.kernel} selects a path without the P2 row plan")
+            if engine.p2_plan() is None:
+                refuse("this P2 basis has no row plan: a DoF numbering without locality, or a vertex with "
+                       "more than 15 neighbours")
+            return FormOperator(
+                engine.n_dofs, engine.dtype, engine.home,
+                lambda: engine.wrap_csr_home(engine.bilinear(alpha, beta)), engine=engine, alpha=alpha, beta=beta,
+                p2_rows=True, matrix_free=True,
+            )
+        if not engine.may_apply_matrix_free():
+            if engine.kernel not in ("auto", "rings"):
+                refuse(f"TFEM_KERNEL={engine.kernel} selects a path without the ring plan")
+            refuse("the DoFs of this P1 basis are not the mesh's vertices: no ring plan")
+        if expr.has_coefficients:
+            if not engine.supports_source():
+                refuse("this basis takes no source programs for the coefficient fields")
+            programs = self._coefficient_programs(expr)
+            if programs is None:
+                refuse("a coefficient field does not fit a source program")
+            if not engine.supports_coefficients():
+                refuse("no ring plan for the coefficient launch (fans without ring form, or long rows)")
+
+            def assemble():
+                return engine.wrap_csr_home(engine.bilinear_coef(alpha, beta, *programs))
+
+            return FormOperator(engine.n_dofs, engine.dtype, engine.home, assemble, engine=engine, alpha=alpha,
+                                beta=beta, programs=programs, matrix_free=True)
+        if engine.ring_plan() is None:
+            refuse("the fans of this P1 mesh have no ring form: no ring plan")
+        return FormOperator(
+            engine.n_dofs, engine.dtype, engine.home,
+            lambda: engine.wrap_csr_home(engine.bilinear(alpha, beta)), engine=engine, alpha=alpha, beta=beta,
+            matrix_free=True,
+        )
 
     def _reduce_integrand(self, integrand):
         """CSR values of a materialised bilinear integrand: the generic reduce + scatter kernels."""
@@ -273,6 +331,8 @@ class AbstractBasis(abc.ABC):
         fused = None
         if isinstance(a_expr, forms.BilinearExpr) and a_expr.has_coefficients:
             # the coefficient K launch, then the load vector's own launch (two launches)
+            return self._bilinear_of(a_expr, layout), self._linear_of(l_expr)
+        if layout == "matrix_free":  # no K to fuse the load vector with: the two calls
             return self._bilinear_of(a_expr, layout), self._linear_of(l_expr)
         if isinstance(a_expr, forms.BilinearExpr) and isinstance(l_expr, forms.LinearExpr) and l_expr.flux is None:
             coefficient = l_expr.coefficient

@@ -1141,18 +1141,66 @@ class AssemblyEngine:
             )
         return y.view(self.n_dofs, k)
 
-    def apply(self, alpha, beta, u, out=None):
-        """(alpha * stiffness + beta * mass) u, matrix-free over the ring plan; u and the result
-        (flat, n_dofs) in the caller's numbering, or (n_dofs, k) for k >= 2 vectors in one launch.
-        ``out``: a preallocated device buffer."""
-        if self._perm is None:
-            return self._apply_rings(alpha, beta, u, out)
+    def may_apply_p2_matrix_free(self):
+        """Whether a P2 row plan CAN exist for this basis (P2 on one mesh, the row kernels not
+        switched away: what p2_plan() tests before it builds) -- known without building it."""
+        return (self.kernel in ("auto", "rows") and self.poly_order == 2 and self.n_fractures == 0
+                and self._host_conn_geo.dim() == 2)
+
+    def _apply_p2_rows(self, alpha, beta, u, out=None):
+        """One tfem_p2_apply_rows call in the ENGINE's numbering: (alpha * stiffness + beta * mass) u
+        of a P2 basis without the CSR values, u None: the diagonal.  A block (n_dofs, k), k >= 2,
+        goes column by column (the same launch per column), result (n_dofs, k)."""
+        rows = self.p2_plan()
+        if rows is None:
+            raise NotImplementedError("the matrix-free P2 operator needs the P2 row plan (a numbering with "
+                                      "locality, at most 15 neighbours per vertex)")
         if _is_block(u):
-            y = self._dofs_out(self._apply_rings_multi(alpha, beta, self._dofs_in(u.to(self.device))))
+            u = u.to(self.device, self.dtype)
+            if u.shape[0] != self.n_dofs:
+                raise ValueError(f"apply: u has {u.shape[0]} rows, the operator {self.n_dofs} columns")
+            k = int(u.shape[1])
+            y = self._output(out, self.n_dofs * k, "operator result").view(self.n_dofs, k)
+            for j in range(k):
+                y[:, j] = self._apply_p2_rows(alpha, beta, u[:, j])
+            return y
+        d = self._inputs()
+        colind = self.csr_structure()[1]
+        if u is not None:
+            u = u.to(self.device, self.dtype).reshape(-1).contiguous()
+            if u.shape[0] != self.n_dofs:
+                raise ValueError(f"apply: u has {u.shape[0]} entries, the operator {self.n_dofs} columns")
+        y = self._output(out, self.n_dofs, "operator result")
+        if u is not None and y.data_ptr() == u.data_ptr():
+            raise ValueError("apply: out must not be u")
+        with torch.cuda.device(self.device):
+            _native.check(
+                self.lib.tfem_p2_apply_rows(
+                    _native.ptr(d["coords"]), self.real_bytes, self.quad_order, float(alpha), float(beta),
+                    _native.ptr(rows["blob"]), c_void_p(rows["layout"].ctypes.data), _native.ptr(colind),
+                    int(colind.shape[0]), _native.ptr(u), _native.ptr(y), self.n_dofs, self._stream(),
+                )
+            )
+        return y
+
+    def _apply_rows(self, alpha, beta, u, out=None):
+        """The matrix-free launch of this basis' polynomial order, in the ENGINE's numbering."""
+        if self.poly_order == 2:
+            return self._apply_p2_rows(alpha, beta, u, out)
+        return self._apply_rings(alpha, beta, u, out)
+
+    def apply(self, alpha, beta, u, out=None):
+        """(alpha * stiffness + beta * mass) u, matrix-free over the ring plan (P1) or the P2 row
+        plan; u and the result (flat, n_dofs) in the caller's numbering, or (n_dofs, k) for k >= 2
+        vectors (P1: in one launch).  ``out``: a preallocated device buffer."""
+        if self._perm is None:
+            return self._apply_rows(alpha, beta, u, out)
+        if _is_block(u):
+            y = self._dofs_out(self._apply_rows(alpha, beta, self._dofs_in(u.to(self.device))))
             if out is not None:
                 return self._output(out, y.numel(), "operator result").copy_(y.reshape(-1)).view(y.shape)
             return y
-        y = self._dofs_out(self._apply_rings(alpha, beta, self._dofs_in(u.to(self.device).reshape(-1))))
+        y = self._dofs_out(self._apply_rows(alpha, beta, self._dofs_in(u.to(self.device).reshape(-1))))
         if out is not None:
             return self._output(out, self.n_dofs, "operator result").copy_(y)
         return y
@@ -1160,7 +1208,7 @@ class AssemblyEngine:
     def operator_diagonal(self, alpha, beta):
         """diag(alpha * stiffness + beta * mass) in the caller's numbering (Jacobi preconditioner),
         from the same launch without u."""
-        return self._dofs_out(self._apply_rings(alpha, beta, None))
+        return self._dofs_out(self._apply_rows(alpha, beta, None))
 
     # ------------------------------------------------------------------ variable coefficients
     def _coef_rings(self):

@@ -297,7 +297,7 @@ class _OperatorApply(torch.autograd.Function):
 
 class FormOperator:
     """The global operator of a bilinear form, to apply and to solve with, without necessarily
-    storing it (``Basis.integrate_bilinear_form(..., layout="operator")``).
+    storing it (``Basis.integrate_bilinear_form(..., layout="operator")`` or ``layout="matrix_free"``).
 
     Matrix-free (``matrix_free`` True): ``alpha * stiffness + beta * mass`` of a P1 basis whose
     engine has a ring plan; every ``matvec`` is one tfem_p1_apply_rings launch that forms the rows
@@ -309,10 +309,17 @@ class FormOperator:
     Vectors are taken and returned in the caller's DoF numbering, of shape (N,) or (N, 1); a block
     (N, k) of k >= 2 vectors gives (N, k): matrix-free with constant coefficients by ONE
     tfem_p1_apply_rings_multi call that forms the rows of K once for the k columns, every other
-    operator by its single-vector launch once per column."""
+    operator by its single-vector launch once per column.
+
+    ``layout="matrix_free"`` is the strict request: the plan is built at the call, the operator it
+    returns is matrix-free from the start (``matrix_free`` True), and a basis or form without the
+    launch raises NotImplementedError there instead of assembling.  It also serves P2 bases
+    (``p2_rows``): ``alpha * stiffness + beta * mass`` over the P2 row plan, every ``matvec`` one
+    tfem_p2_apply_rows call (vertex rows, long vertex rows, edge rows) that reads the pattern's
+    column indices but no values; a block goes column by column."""
 
     def __init__(self, n, dtype, device, assemble, engine=None, alpha=0.0, beta=0.0, symmetric=True,
-                 programs=None):
+                 programs=None, p2_rows=False, matrix_free=None):
         self.shape = (int(n), int(n))
         self.dtype = dtype
         self.device = device
@@ -323,7 +330,10 @@ class FormOperator:
         self._programs = programs
         self._symmetric = symmetric
         self._csr = None
-        self._matrix_free = None if engine is not None else False
+        #: P2 over the row plan (tfem_p2_apply_rows) instead of P1 over the ring plan
+        self._p2_rows = bool(p2_rows)
+        # matrix_free True: decided by the caller, who has built the plan (layout="matrix_free")
+        self._matrix_free = (matrix_free if engine is not None else False)
 
     @classmethod
     def from_csr(cls, csr, symmetric=False):
@@ -346,6 +356,8 @@ class FormOperator:
         """K u (u None: diag K) by one launch in the engine's numbering."""
         if self._programs is not None:
             return self._engine._apply_rings_coef(self.alpha, self.beta, *self._programs, u)
+        if self._p2_rows:
+            return self._engine._apply_p2_rows(self.alpha, self.beta, u)
         return self._engine._apply_rings(self.alpha, self.beta, u)
 
     def to_csr(self):
@@ -452,4 +464,6 @@ class FormOperator:
         kind = "matrix-free" if self._matrix_free else ("CSR" if self._matrix_free is False else "unresolved")
         if self._programs is not None and self._matrix_free is not False:
             kind = "matrix-free, variable coefficients" if self._matrix_free else "unresolved, variable coefficients"
+        if self._p2_rows and self._matrix_free:
+            kind = "matrix-free, P2 rows"
         return f"FormOperator(shape={self.shape}, dtype={self.dtype}, device={self.device}, {kind})"
