@@ -572,6 +572,56 @@ int tfem_p2_apply_rows(const void *coords, int real_bytes, int quad_order, doubl
                        void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The vector part of the Jacobi-preconditioned CG loop around any of the applies above (the loop
+ * that stands where the reference's dense reduce + torch.linalg.solve stops being possible,
+ * abstract_basis.py:114-117,177-195): per iteration
+ *   AP = K P (an apply), tfem_cg_dot, tfem_cg_update, tfem_cg_direction
+ * with alpha, beta and every dot product kept on the device.  All vectors DEVICE, n x n_vec reals
+ * of real_bytes 4 or 8, ROW-major (the n_vec values of a DoF consecutive: the layout of
+ * tfem_p1_apply_rings_multi); n_vec = 1 is the single-vector loop.  Arrays aligned to 16 bytes with
+ * n_vec in {1, 2, 4, 8} are moved 16 bytes at a time, everything else by passes over 8 columns.
+ *   inv_diag (n reals): mask / diag(K).  It doubles as the mask: inv_diag[i] == 0 marks a HELD DoF
+ *            (outside `free`).  A held row is never written by update / direction and takes no part
+ *            in any sum (it is skipped, not multiplied by 0: its Ap may be anything, NaN included).
+ *   active   (n_vec int32): 0 freezes a column -- alpha = beta = 0 and nothing of it is written.
+ *   ws       the caller's workspace of tfem_cg_workspace_bytes(n, n_vec) bytes, need not be
+ *            initialised: 5 buffers of G x n_vec doubles [workgroup][column], G = bytes / (40 n_vec)
+ *            a function of n alone: p.Ap | r.z parity 0 | r.r parity 0 | r.z parity 1 | r.r parity 1.
+ *            Every launch writes one partial sum per workgroup and column (double, also for float
+ *            vectors); a later launch sums the G partials of a column itself, every workgroup in the
+ *            same order -- no atomics, the same bits in every run.  sum over axis 0 of the r.r buffer
+ *            of parity step & 1 is |r|^2 per column after tfem_cg_update(step).
+ *   step     iteration number >= 0; its parity picks the buffers: update(step) reads r.z of parity
+ *            (step - 1) & 1 and writes parity step & 1, direction(step) reads both.
+ * start:     p = inv_diag * r (0 on held rows); partials of r.(inv_diag * r) and r.r into parity 1,
+ *            the one step 0 reads as "previous".
+ * dot:       partials of sum p * ap per column over the rows that are not held.
+ * update:    alpha_j = active[j] ? r.z_j / p.Ap_j : 0; x += alpha p, r -= alpha ap on the rows that
+ *            are not held; partials of r.(inv_diag * r) and r.r (all columns) into parity step & 1.
+ * direction: beta_j = r.z_j(step) / r.z_j(step - 1); p = inv_diag * r + beta p for active columns
+ *            on the rows that are not held.
+ * One launch each; no allocation, no synchronisation.  TFEM_ERR_INVALID_ARGUMENT: real_bytes not 4
+ * or 8, a negative size or step, a NULL array with n > 0 and n_vec > 0; TFEM_ERR_INDEX_RANGE: a
+ * vector of 4 GiB or more (rows and entries are counted in 32 bits).  Nothing is launched after a
+ * refusal; n == 0 or n_vec == 0 succeeds and launches nothing.
+ * tfem_cg_workspace_bytes (HOST): > 0 for n >= 0, n_vec >= 1; -1 for a negative argument or for
+ * vectors the launches refuse (so the size always fits the int it is returned in).
+ * tfem_cg_constant (HOST): what = 0 lanes per workgroup, 1 the cap of G, 2 columns per pass.
+ * ------------------------------------------------------------------------- */
+int tfem_cg_workspace_bytes(int64_t n, int64_t n_vec);
+int tfem_cg_constant(int what);
+int tfem_cg_start(const void *r, const void *inv_diag, void *p, int real_bytes, int64_t n,
+                  int64_t n_vec, void *ws, void *stream);
+int tfem_cg_dot(const void *p, const void *ap, const void *inv_diag, int real_bytes, int64_t n,
+                int64_t n_vec, void *ws, void *stream);
+int tfem_cg_update(void *x, void *r, const void *p, const void *ap, const void *inv_diag,
+                   const int32_t *active, int real_bytes, int64_t n, int64_t n_vec, int64_t step,
+                   void *ws, void *stream);
+int tfem_cg_direction(void *p, const void *r, const void *inv_diag, const int32_t *active,
+                      int real_bytes, int64_t n, int64_t n_vec, int64_t step, const void *ws,
+                      void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Interface exchange of the multi-GPU sharding (DEVICE; the path shards by element
  * range, DoFs on an inter-rank interface are summed with one all-reduce of a packed
  * buffer: SURVEY 8(e); the reference is single-process).  pack: buf (nbuf) is zeroed,

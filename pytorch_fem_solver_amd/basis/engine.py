@@ -1099,7 +1099,6 @@ class AssemblyEngine:
         rings = self.ring_plan()
         if rings is None:
             raise NotImplementedError("the matrix-free operator needs the ring plan (P1, fans with a ring form)")
-        d = self._inputs()
         if u is not None:
             u = u.to(self.device, self.dtype).reshape(-1).contiguous()
             if u.shape[0] != self.n_dofs:
@@ -1108,13 +1107,7 @@ class AssemblyEngine:
         if u is not None and y.data_ptr() == u.data_ptr():
             raise ValueError("apply: out must not be u")
         with torch.cuda.device(self.device):
-            _native.check(
-                self.lib.tfem_p1_apply_rings(
-                    _native.ptr(d["coords"]), self.real_bytes, self.n_dofs, self.quad_order, float(alpha),
-                    float(beta), _native.ptr(rings["blob"]), c_void_p(rings["layout"].ctypes.data),
-                    _native.ptr(u), _native.ptr(y), self._stream(),
-                )
-            )
+            self._apply_launch(alpha, beta, u, y)()
         return y
 
     def _apply_rings_multi(self, alpha, beta, u, out=None):
@@ -1123,7 +1116,6 @@ class AssemblyEngine:
         rings = self.ring_plan()
         if rings is None:
             raise NotImplementedError("the matrix-free operator needs the ring plan (P1, fans with a ring form)")
-        d = self._inputs()
         u = u.to(self.device, self.dtype).contiguous()  # row-major: a vertex's k values are consecutive
         if u.shape[0] != self.n_dofs:
             raise ValueError(f"apply: u has {u.shape[0]} rows, the operator {self.n_dofs} columns")
@@ -1132,13 +1124,7 @@ class AssemblyEngine:
         if y.data_ptr() == u.data_ptr():
             raise ValueError("apply: out must not be u")
         with torch.cuda.device(self.device):
-            _native.check(
-                self.lib.tfem_p1_apply_rings_multi(
-                    _native.ptr(d["coords"]), self.real_bytes, self.n_dofs, self.quad_order, float(alpha),
-                    float(beta), _native.ptr(rings["blob"]), c_void_p(rings["layout"].ctypes.data),
-                    _native.ptr(u), _native.ptr(y), k, self._stream(),
-                )
-            )
+            self._apply_launch(alpha, beta, u, y, k=k)()
         return y.view(self.n_dofs, k)
 
     def may_apply_p2_matrix_free(self):
@@ -1164,8 +1150,6 @@ class AssemblyEngine:
             for j in range(k):
                 y[:, j] = self._apply_p2_rows(alpha, beta, u[:, j])
             return y
-        d = self._inputs()
-        colind = self.csr_structure()[1]
         if u is not None:
             u = u.to(self.device, self.dtype).reshape(-1).contiguous()
             if u.shape[0] != self.n_dofs:
@@ -1174,13 +1158,7 @@ class AssemblyEngine:
         if u is not None and y.data_ptr() == u.data_ptr():
             raise ValueError("apply: out must not be u")
         with torch.cuda.device(self.device):
-            _native.check(
-                self.lib.tfem_p2_apply_rows(
-                    _native.ptr(d["coords"]), self.real_bytes, self.quad_order, float(alpha), float(beta),
-                    _native.ptr(rows["blob"]), c_void_p(rows["layout"].ctypes.data), _native.ptr(colind),
-                    int(colind.shape[0]), _native.ptr(u), _native.ptr(y), self.n_dofs, self._stream(),
-                )
-            )
+            self._apply_launch(alpha, beta, u, y)()
         return y
 
     def _apply_rows(self, alpha, beta, u, out=None):
@@ -1269,7 +1247,6 @@ class AssemblyEngine:
         rings = self._coef_rings()
         if rings is None:
             raise NotImplementedError("the variable-coefficient operator needs a ring plan without long rows (P1)")
-        d = self._inputs()
         if u is not None:
             u = u.to(self.device, self.dtype).reshape(-1).contiguous()
             if u.shape[0] != self.n_dofs:
@@ -1278,13 +1255,7 @@ class AssemblyEngine:
         if u is not None and y.data_ptr() == u.data_ptr():
             raise ValueError("apply: out must not be u")
         with torch.cuda.device(self.device):
-            _native.check(
-                self.lib.tfem_p1_apply_rings_coef(
-                    _native.ptr(d["coords"]), self.real_bytes, self.n_dofs, self.quad_order, float(alpha),
-                    float(beta), self._program_ref(kappa), self._program_ref(c), _native.ptr(rings["blob"]),
-                    c_void_p(rings["layout"].ctypes.data), _native.ptr(u), _native.ptr(y), self._stream(),
-                )
-            )
+            self._apply_launch(alpha, beta, u, y, programs=(kappa, c))()
         return y
 
     def apply_coef(self, alpha, beta, kappa, c, u, out=None):
@@ -1305,6 +1276,77 @@ class AssemblyEngine:
     def operator_diagonal_coef(self, alpha, beta, kappa, c):
         """diag(K) of the variable-coefficient form in the caller's numbering."""
         return self._dofs_out(self._apply_rings_coef(alpha, beta, kappa, c, None))
+
+    def _prepared_apply(self, alpha, beta, u, y, programs=None):
+        """The matrix-free launch y = K u in the ENGINE's numbering with every argument converted
+        ONCE (the loop of sparse.fused_conjugate_gradients applies the same two buffers every
+        iteration): the returned callable only enqueues, on the stream that is current NOW.  u and
+        y: contiguous device tensors of this engine's dtype, (n_dofs,) or (n_dofs, k); P1 constant
+        coefficients take a block in one tfem_p1_apply_rings_multi call, the coefficient and the P2
+        launches go column by column through a contiguous pair of columns."""
+        for t in (u, y):
+            if t.dtype != self.dtype or t.device != self.device or not t.is_contiguous() or t.shape[0] != self.n_dofs:
+                raise ValueError(f"prepared apply: contiguous {self.dtype} tensors of {self.n_dofs} rows on {self.device}")
+        if u.shape != y.shape or u.data_ptr() == y.data_ptr():
+            raise ValueError("prepared apply: u and y must be two tensors of one shape")
+        k = int(u.shape[1]) if _is_block(u) else 1
+        multi = k > 1 and programs is None and self.poly_order == 1
+        if k > 1 and not multi:
+            u_col, y_col = (torch.empty(self.n_dofs, dtype=self.dtype, device=self.device) for _ in range(2))
+            one = self._prepared_apply(alpha, beta, u_col, y_col, programs)
+
+            def columns():
+                for j in range(k):
+                    u_col.copy_(u[:, j])
+                    one()
+                    y[:, j].copy_(y_col)
+
+            return columns
+        return self._apply_launch(alpha, beta, u, y, programs, k)
+
+    def _apply_launch(self, alpha, beta, u, y, programs=None, k=1):
+        """THE call of the matrix-free apply launches (tfem_p1_apply_rings, _multi for k >= 2,
+        _coef with `programs` = (kappa, c), tfem_p2_apply_rows on P2) with its arguments converted:
+        y = K u in the engine's numbering, u None: the diagonal; u and y as the callers have
+        checked them.  The returned callable enqueues on the stream that is current now."""
+        d = self._inputs()
+        head = (_native.ptr(d["coords"]), self.real_bytes)
+        scale = (float(alpha), float(beta))
+        tail = (_native.ptr(u), _native.ptr(y))
+        stream = self._stream()
+        if self.poly_order == 2:
+            plan = self.p2_plan()
+            if plan is None:
+                raise NotImplementedError("the matrix-free P2 operator needs the P2 row plan")
+            colind = self.csr_structure()[1]
+            fn = self.lib.tfem_p2_apply_rows
+            args = (*head, self.quad_order, *scale, _native.ptr(plan["blob"]), c_void_p(plan["layout"].ctypes.data),
+                    _native.ptr(colind), int(colind.shape[0]), *tail, self.n_dofs, stream)
+        else:
+            plan = self.ring_plan() if programs is None else self._coef_rings()
+            if plan is None:
+                raise NotImplementedError("the matrix-free operator needs the ring plan (P1, fans with a ring form)")
+            where = (_native.ptr(plan["blob"]), c_void_p(plan["layout"].ctypes.data))
+            head = (*head, self.n_dofs, self.quad_order, *scale)
+            if programs is not None:
+                fn = self.lib.tfem_p1_apply_rings_coef
+                args = (*head, self._program_ref(programs[0]), self._program_ref(programs[1]), *where, *tail, stream)
+            elif k > 1:
+                fn = self.lib.tfem_p1_apply_rings_multi
+                args = (*head, *where, *tail, k, stream)
+            else:
+                fn = self.lib.tfem_p1_apply_rings
+                args = (*head, *where, *tail, stream)
+        keep = (d, plan, u, y, programs)  # what the raw pointers above point into
+        check = _native.check
+
+        def launch():
+            status = fn(*args)
+            if status:
+                check(status)
+            return keep[3]
+
+        return launch
 
     def prepared_system(self, alpha, beta, out, fq=None, source=None, tiles=None):
         """The launch of assemble_system(alpha, beta, fq | source, out=out, tiles=tiles) with every

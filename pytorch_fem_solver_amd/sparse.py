@@ -7,9 +7,28 @@ materialises the reference's layout when it fits.
 
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import _native
+
+#: TFEM_CG=torch: solve_cg / solve_cg_multi keep the loop of torch operations on the GPU as well
+#: (read once, here: the solve path asks no environment variable).  Anything else: the fused loop.
+_CG_LOOP = "torch" if os.environ.get("TFEM_CG", "").strip().lower() == "torch" else "fused"
+
+
+def _cg_loop(loop, device):
+    """The loop a solve runs: ``loop`` ("fused" | "torch" | None = the default: fused on a HIP
+    device unless TFEM_CG=torch, the torch loop on the host)."""
+    if loop not in (None, "fused", "torch"):
+        raise ValueError(f"loop must be None, 'fused' or 'torch', not {loop!r}")
+    on_gpu = torch.device(device).type == "cuda"
+    if loop == "fused" and not on_gpu:
+        raise ValueError("loop='fused': the fused CG kernels need the vectors on a HIP device")
+    if loop is None:
+        return _CG_LOOP if on_gpu else "torch"
+    return loop
 
 
 class CSRMatrix:
@@ -124,14 +143,42 @@ class CSRMatrix:
             raise ValueError(f"matvec: x has {flat.shape[0]} entries, the operator {self.shape[1]} columns")
         y = torch.empty(self.shape[0], dtype=self.dtype, device=self.device)
         with torch.cuda.device(self.device):
-            _native.check(
-                lib.tfem_csr_spmv(
-                    _native.ptr(self.crow_indices), _native.ptr(self.col_indices), _native.ptr(self.values),
-                    self.values.element_size(), self.shape[0], _native.ptr(flat), _native.ptr(y),
-                    _native.current_stream(self.device),
-                )
-            )
+            self._prepared_spmv(flat, y)()
         return y.reshape(x.shape)
+
+    def _prepared_spmv(self, x, y):
+        """y = A x in the STORED numbering into a given y, nothing allocated: x and y contiguous
+        device tensors of the operator's dtype, (N,) or (N, k) (a block: the launch once per column
+        through a contiguous pair of columns).  The arguments are converted once; the returned
+        callable only enqueues, on the stream that is current now."""
+        n = self.shape[0]
+        for t, rows in ((x, self.shape[1]), (y, n)):
+            if t.dtype != self.dtype or t.device != self.device or not t.is_contiguous() or t.shape[0] != rows:
+                raise ValueError(f"spmv: contiguous {self.dtype} tensors of {rows} rows on {self.device}")
+        if _is_block(x):
+            k = x.shape[1]
+            x_col, y_col = (torch.empty(rows, dtype=self.dtype, device=self.device) for rows in (self.shape[1], n))
+            one = self._prepared_spmv(x_col, y_col)
+
+            def columns():
+                for j in range(k):
+                    x_col.copy_(x[:, j])
+                    one()
+                    y[:, j].copy_(y_col)
+
+            return columns
+        fn = _native.load().tfem_csr_spmv
+        args = (_native.ptr(self.crow_indices), _native.ptr(self.col_indices), _native.ptr(self.values),
+                self.values.element_size(), n, _native.ptr(x), _native.ptr(y), _native.current_stream(self.device))
+        keep = (self, x, y)  # what the raw pointers above point into
+
+        def launch():
+            status = fn(*args)
+            if status:
+                _native.check(status)
+            return keep[2]
+
+        return launch
 
     def diagonal(self):
         """Diagonal entries (0 where a row stores none)."""
@@ -145,31 +192,44 @@ class CSRMatrix:
         diag[rows[hit]] = self.values[hit]
         return diag
 
-    def solve_cg(self, b, free=None, x0=None, rtol=1e-12, maxiter=None):
+    def solve_cg(self, b, free=None, x0=None, rtol=1e-12, maxiter=None, loop=None):
         """Jacobi-preconditioned conjugate gradients for the symmetric positive definite
         operator restricted to the DoFs `free` (index tensor; the others keep x0's values, 0 by
         default: homogeneous Dirichlet rows and columns are simply masked, no submatrix is
         formed).  Returns (x, iterations, relative residual).  Stands where the reference's
         dense `reduce` + `torch.linalg.solve` (abstract_basis.py:114-117,177-195) stops being
-        possible."""
+        possible.  On the GPU the loop is ``fused_conjugate_gradients`` (the SpMV
+        and three tfem_cg_* launches per iteration); ``loop="torch"`` or TFEM_CG=torch keeps the loop
+        of torch operations (``conjugate_gradients``), ``loop="fused"`` insists on the kernels."""
+        which = _cg_loop(loop, self.device)
         if self.perm is not None:  # solve in the stored numbering, vectors translated at the boundary
             inv = self._inverse()
             to_stored = lambda v: None if v is None else v.to(self.device, self.dtype).reshape(-1)[self.perm]  # noqa: E731
             free_s = None if free is None else inv[free.to(self.device).reshape(-1)]
-            x, it, res = self._stored().solve_cg(to_stored(b), free_s, to_stored(x0), rtol, maxiter)
+            x, it, res = self._stored().solve_cg(to_stored(b), free_s, to_stored(x0), rtol, maxiter, which)
             return x[inv].reshape(b.shape), it, res
-        x, it, res = conjugate_gradients(self.matvec, self.diagonal(), b, free, x0, rtol, maxiter)
+        if which == "fused":
+            x, it, res = fused_conjugate_gradients(_into(self._prepared_spmv), self.diagonal(), b.reshape(-1), free,
+                                                   None if x0 is None else x0.reshape(-1), rtol, maxiter)
+        else:
+            x, it, res = conjugate_gradients(self.matvec, self.diagonal(), b, free, x0, rtol, maxiter)
         return x.reshape(b.shape), it, res
 
-    def solve_cg_multi(self, B, free=None, X0=None, rtol=1e-12, maxiter=None):
-        """``solve_cg`` for the k columns of B (N, k) at once (``conjugate_gradients_multi``): one
-        block application per iteration.  Returns (X (N, k), iterations (k,), relative residuals (k,))."""
+    def solve_cg_multi(self, B, free=None, X0=None, rtol=1e-12, maxiter=None, loop=None):
+        """``solve_cg`` for the k columns of B (N, k) at once (``conjugate_gradients_multi``, on the
+        GPU ``fused_conjugate_gradients``; ``loop`` as in ``solve_cg``): one block application per
+        iteration.  Returns (X (N, k), iterations (k,), relative residuals (k,))."""
+        which = _cg_loop(loop, self.device)
         if self.perm is not None:  # solve in the stored numbering, rows translated at the boundary
             inv = self._inverse()
             to_stored = lambda v: None if v is None else v.to(self.device, self.dtype)[self.perm]  # noqa: E731
             free_s = None if free is None else inv[free.to(self.device).reshape(-1)]
-            X, it, res = self._stored().solve_cg_multi(to_stored(B), free_s, to_stored(X0), rtol, maxiter)
+            X, it, res = self._stored().solve_cg_multi(to_stored(B), free_s, to_stored(X0), rtol, maxiter, which)
             return X[inv], it, res
+        if which == "fused":
+            if B.dim() != 2 or B.shape[0] != self.shape[0]:
+                raise ValueError(f"solve_cg_multi: B must have shape ({self.shape[0]}, k)")
+            return fused_conjugate_gradients(_into(self._prepared_spmv), self.diagonal(), B, free, X0, rtol, maxiter)
         return conjugate_gradients_multi(self.matvec, self.diagonal(), B, free, X0, rtol, maxiter)
 
     def __repr__(self):
@@ -272,6 +332,116 @@ def conjugate_gradients_multi(matvec, diagonal, B, free=None, X0=None, rtol=1e-1
             running = active.cpu()
     its[running] = it
     res = torch.linalg.vector_norm(R, dim=0) / b_norm
+    return X, its, res.cpu()
+
+
+def _into(prepare):
+    """``matvec_into(u, out)`` for ``fused_conjugate_gradients`` from a ``prepare(u, out)`` that
+    returns the launch with its arguments converted: one preparation per pair of buffers (the loop
+    applies the same pair every iteration), then only the enqueue."""
+    prepared = {}
+
+    def matvec_into(u, out):
+        key = (u.data_ptr(), out.data_ptr(), tuple(u.shape))
+        launch = prepared.get(key)
+        if launch is None:
+            launch = prepared[key] = prepare(u, out)
+        launch()
+
+    return matvec_into
+
+
+def cg_constants():
+    """(lanes per workgroup, cap of the number of workgroups, columns per pass) of the tfem_cg_*
+    launches (csrc/tfem_cg.hip)."""
+    lib = _native.load()
+    return tuple(int(lib.tfem_cg_constant(i)) for i in range(3))
+
+
+def cg_workspace(n, k, device):
+    """The workspace of the tfem_cg_* launches for n x k vectors, as a (5, G, k) float64 tensor:
+    per-workgroup partial sums of p.Ap | r.z, r.r of parity 0 | r.z, r.r of parity 1."""
+    size = int(_native.load().tfem_cg_workspace_bytes(n, k))
+    if size < 0:
+        raise ValueError(f"fused CG: vectors of {n} x {k} entries are beyond the kernels' 32-bit extent")
+    return torch.empty(size // 8, dtype=torch.float64, device=device).view(5, -1, k)
+
+
+def fused_conjugate_gradients(matvec_into, diagonal, B, free=None, X0=None, rtol=1e-12, maxiter=None):
+    """``conjugate_gradients`` (B of shape (N,)) and ``conjugate_gradients_multi`` (B of shape
+    (N, k)) on a HIP device with the vector part in libtfem_hip (csrc/tfem_cg.hip): per iteration
+    ``matvec_into(P, AP)`` (writes A P into the preallocated AP, same shape as B) and three
+    launches -- tfem_cg_dot, tfem_cg_update, tfem_cg_direction -- with alpha, beta and the dot
+    products on the device; the host reads |r|^2 from the workspace at the check every 25
+    iterations and at maxiter, as the torch loops do.  The same recurrence, contract and return
+    values: (x, iterations, relative residual), or (X, iterations (k,), residuals (k,)) with the
+    last two on the host for a block (the residuals in float64: the sums are kept in double).  A column that starts converged takes no iteration; a frozen
+    column's direction is zeroed at the check and its x and r are never written again."""
+    lib = _native.load()
+    n = diagonal.shape[0]
+    dtype, device = diagonal.dtype, diagonal.device
+    if device.type != "cuda":
+        raise ValueError("fused_conjugate_gradients: the vectors must be on a HIP device")
+    single = B.dim() == 1
+    B = B.to(device, dtype)
+    if B.shape[0] != n or B.dim() > 2:
+        raise ValueError(f"fused_conjugate_gradients: B must have shape ({n},) or ({n}, k)")
+    B = B.reshape(n, -1)
+    k = B.shape[1]
+    shape = (n,) if single else (n, k)
+    mask = torch.ones(n, 1, dtype=dtype, device=device)
+    if free is not None:
+        mask.zero_()
+        mask[free.to(device).reshape(-1)] = 1
+    X = torch.zeros(n, k, dtype=dtype, device=device) if X0 is None else X0.to(device, dtype).reshape(n, k).clone(memory_format=torch.contiguous_format)
+    diag = diagonal.reshape(n, 1)
+    inv_diag = (mask / torch.where(diag != 0, diag, torch.ones_like(diag))).reshape(-1).contiguous()
+    AP, P = torch.empty(n, k, dtype=dtype, device=device), torch.empty(n, k, dtype=dtype, device=device)
+    maxiter = maxiter or 10 * n
+    its = torch.zeros(k, dtype=torch.int64, device="cpu")
+    with torch.cuda.device(device):
+        matvec_into(X.view(shape), AP.view(shape))
+        R = mask * (B - AP)
+        b_norm = torch.linalg.vector_norm(mask * B, dim=0).clamp_min(torch.finfo(dtype).tiny)
+        res = torch.linalg.vector_norm(R, dim=0) / b_norm
+        active = res > rtol  # (k,) on the device; its host copy decides the loop
+        running = active.cpu()
+        it = 0
+        res0, flags0 = res.double(), active
+        res = res0
+        if n > 0 and k > 0 and maxiter > 0 and bool(running.any()):
+            ws = cg_workspace(n, k, device)
+            flags = active.to(torch.int32)
+            stream = _native.current_stream(device)
+            size = (B.element_size(), n, k)
+            x_, r_, p_, ap_, d_, f_, w_ = (_native.ptr(t) for t in (X, R, P, AP, inv_diag, flags, ws))
+            _native.check(lib.tfem_cg_start(r_, d_, p_, *size, w_, stream))
+            if not bool(running.all()):
+                P *= active
+            dot, update, direction = lib.tfem_cg_dot, lib.tfem_cg_update, lib.tfem_cg_direction
+            dot_args = (p_, ap_, d_, *size, w_, stream)
+            P_view, AP_view = P.view(shape), AP.view(shape)
+            b_norm2 = b_norm.double()
+            while it < maxiter and bool(running.any()):
+                matvec_into(P_view, AP_view)
+                status = (dot(*dot_args) or update(x_, r_, p_, ap_, d_, f_, *size, it, w_, stream)
+                          or direction(p_, r_, d_, f_, *size, it, w_, stream))
+                if status:
+                    _native.check(status)
+                it += 1
+                if it % 25 == 0 or it == maxiter:  # one host synchronisation every 25 iterations
+                    res = ws[2 + 2 * ((it - 1) & 1)].sum(0).sqrt() / b_norm2
+                    its[running] = it
+                    active = active & (res > rtol)
+                    P *= active
+                    flags.copy_(active)
+                    running = active.cpu()
+            its[running] = it
+            # the loop ended at a check: what it decided on is what is reported (a column that
+            # took no iteration keeps the residual of the set-up)
+            res = torch.where(flags0, res, res0)
+    if single:
+        return X.reshape(-1), int(its[0]), float(res[0])
     return X, its, res.cpu()
 
 
@@ -408,12 +578,20 @@ class FormOperator:
             return engine._home(engine.operator_diagonal(self.alpha, self.beta))
         return self.to_csr().diagonal()
 
-    def solve_cg(self, b, free=None, x0=None, rtol=1e-12, maxiter=None):
+    def _rows_into(self):
+        """``matvec_into`` of ``fused_conjugate_gradients``: the launch of ``_rows`` into a given
+        buffer, in the engine's numbering."""
+        programs = self._programs
+        return _into(lambda u, out: self._engine._prepared_apply(self.alpha, self.beta, u, out, programs))
+
+    def solve_cg(self, b, free=None, x0=None, rtol=1e-12, maxiter=None, loop=None):
         """Jacobi-preconditioned CG on the DoFs ``free``: the contract and the results of
-        ``CSRMatrix.solve_cg``.  Matrix-free, every iteration is one apply launch, and the loop
-        runs in the engine's numbering (vectors translated once at the boundary)."""
+        ``CSRMatrix.solve_cg`` (``loop`` included).  Matrix-free, every iteration is one apply launch
+        (and, in the fused loop, three tfem_cg_* launches), and the loop runs in the engine's
+        numbering (vectors translated once at the boundary)."""
         if not self.matrix_free:
-            return self.to_csr().solve_cg(b, free, x0, rtol, maxiter)
+            return self.to_csr().solve_cg(b, free, x0, rtol, maxiter, loop)
+        which = _cg_loop(loop, self._engine.device)
         engine = self._engine
         dev, dtype = engine.device, engine.dtype
         inv = None if engine._inv is None else engine._inv.to(dev)
@@ -426,18 +604,25 @@ class FormOperator:
             free_e = free.to(dev).reshape(-1)
             if inv is not None:
                 free_e = inv[free_e]
-        x, it, res = conjugate_gradients(
-            self._rows, self._rows(None),
-            inward(b), free_e, inward(x0), rtol, maxiter,
-        )
+        if which == "fused":
+            x, it, res = fused_conjugate_gradients(
+                self._rows_into(), self._rows(None), inward(b), free_e, inward(x0), rtol, maxiter,
+            )
+        else:
+            x, it, res = conjugate_gradients(
+                self._rows, self._rows(None),
+                inward(b), free_e, inward(x0), rtol, maxiter,
+            )
         return engine._home(engine._dofs_out(x)).reshape(b.shape), it, res
 
-    def solve_cg_multi(self, B, free=None, X0=None, rtol=1e-12, maxiter=None):
+    def solve_cg_multi(self, B, free=None, X0=None, rtol=1e-12, maxiter=None, loop=None):
         """``solve_cg`` for the k columns of B (N, k) at once: one block apply per iteration
-        (``conjugate_gradients_multi``), in the engine's numbering when matrix-free.  Returns
+        (``conjugate_gradients_multi``, on the GPU ``fused_conjugate_gradients``; ``loop`` as in
+        ``solve_cg``), in the engine's numbering when matrix-free.  Returns
         (X (N, k), iterations (k,), relative residuals (k,))."""
         if not self.matrix_free:
-            return self.to_csr().solve_cg_multi(B, free, X0, rtol, maxiter)
+            return self.to_csr().solve_cg_multi(B, free, X0, rtol, maxiter, loop)
+        which = _cg_loop(loop, self._engine.device)
         engine = self._engine
         dev, dtype = engine.device, engine.dtype
         inv = None if engine._inv is None else engine._inv.to(dev)
@@ -453,9 +638,13 @@ class FormOperator:
             free_e = free.to(dev).reshape(-1)
             if inv is not None:
                 free_e = inv[free_e]
-        X, it, res = conjugate_gradients_multi(
-            self._rows, self._rows(None), inward(B), free_e, inward(X0), rtol, maxiter,
-        )
+        if which == "fused":
+            if B.dim() != 2 or B.shape[0] != self.shape[0]:
+                raise ValueError(f"solve_cg_multi: B must have shape ({self.shape[0]}, k)")
+            solver, matvec = fused_conjugate_gradients, self._rows_into()
+        else:
+            solver, matvec = conjugate_gradients_multi, self._rows
+        X, it, res = solver(matvec, self._rows(None), inward(B), free_e, inward(X0), rtol, maxiter)
         if inv is not None:
             X = X.index_select(0, inv)
         return engine._home(X), it, res

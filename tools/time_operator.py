@@ -1,7 +1,7 @@
 """Developer tool (GPU box): the matrix-free P1 operator (tfem_p1_apply_rings) against the CSR
 SpMV on the assembled operator of the same mesh, the K-only assembly launch, and CG per iteration.
 
-    python tools/time_operator.py [n] [--cg-n 1000] [--no-cg] [--reps 200]
+    python tools/time_operator.py [n] [--cg-n 1000] [--no-cg] [--cg-loop both] [--reps 200]
 
 S(n) (default 2236: 9,999,392 elements), fp64, stiffness.  Every launch timed with events over
 `reps` back-to-back launches after a warm-up (steady state); run under
@@ -47,6 +47,8 @@ def main():
     p.add_argument("n", type=int, nargs="?", default=2236)
     p.add_argument("--cg-n", type=int, default=1000)
     p.add_argument("--no-cg", action="store_true")
+    p.add_argument("--cg-loop", choices=("torch", "fused", "both"), default="both",
+                   help="the CG loop to time: the torch operations, the tfem_cg_* launches, or one after the other")
     p.add_argument("--reps", type=int, default=200)
     args = p.parse_args()
     torch.set_default_dtype(torch.float64)
@@ -97,16 +99,19 @@ def main():
         lambda b: 2.0 * math.pi**2 * torch.sin(math.pi * b.integration_points[..., [0]])
         * torch.sin(math.pi * b.integration_points[..., [1]]) * b.v)
     free = basis._basis_parameters["inner_dofs"]
-    op.solve_cg(f, free=free, maxiter=50)  # plan, warm-up
-    K.solve_cg(f, free=free, maxiter=50)
+    loops = ("torch", "fused") if args.cg_loop == "both" else (args.cg_loop,)
+    for loop in loops:
+        op.solve_cg(f, free=free, maxiter=50, loop=loop)  # plan, warm-up
+        K.solve_cg(f, free=free, maxiter=50, loop=loop)
     for name, A in (("operator", op), ("CSR", K)):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        x, it, res = A.solve_cg(f, free=free, rtol=1e-10)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print(f"CG {name:8s} S({args.cg_n}) {K.shape[0]} DoFs: {it} iterations, residual {res:.1e}, {dt:.3f} s, "
-              f"{dt / it * 1e6:.1f} us per iteration")
+        for loop in loops:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            x, it, res = A.solve_cg(f, free=free, rtol=1e-10, loop=loop)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print(f"CG {name:8s} {loop:5s} loop S({args.cg_n}) {K.shape[0]} DoFs: {it} iterations, residual {res:.1e}, "
+                  f"{dt:.3f} s, {dt / it * 1e6:.1f} us per iteration")
 
 
 if __name__ == "__main__":

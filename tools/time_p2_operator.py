@@ -1,7 +1,7 @@
 """Developer tool (GPU box): the matrix-free P2 operator (tfem_p2_apply_rows, layout="matrix_free")
 against tfem_csr_spmv on the assembled K of the same basis, and CG with each.
 
-    python tools/time_p2_operator.py [n] [--delaunay 200000] [--blocks 10] [--per-block 20] [--cg-iters 200]
+    python tools/time_p2_operator.py [n] [--delaunay 200000] [--blocks 10] [--per-block 20] [--cg-iters 200] [--cg-loop both]
 
 S(n) (default 707: 999,698 elements, BASELINE config 3) with ElementTri(2, 2), fp64, stiffness; then
 the Morton-permuted Delaunay mesh D(200000, 2) (vertices with 8 .. 15 neighbours: long rows).  One
@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 import pytorch_fem_solver_amd as tf  # noqa: E402
 from pytorch_fem_solver_amd import meshgen  # noqa: E402
-from pytorch_fem_solver_amd.sparse import conjugate_gradients  # noqa: E402
+from pytorch_fem_solver_amd.sparse import _into, conjugate_gradients, fused_conjugate_gradients  # noqa: E402
 
 HBM = 8e12  # bytes/s, MI355X peak
 
@@ -92,16 +92,21 @@ def measure(label, mesh_np, args):
     if eng.renumbered:
         free = eng._inv.to(free.device)[free]
     diag = eng._apply_p2_rows(1.0, 0.0, None)
-    for name, fn, dg in (("matrix-free apply", lambda v: eng._apply_p2_rows(1.0, 0.0, v), diag),
-                         ("SpMV on K", Ks.matvec, Ks.diagonal())):
-        conjugate_gradients(fn, dg, f, free, None, 0.0, 25)  # warm-up
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        _, it, res = conjugate_gradients(fn, dg, f, free, None, 0.0, args.cg_iters)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print(f"  CG with {name:18s} {it} iterations in {dt * 1e3:7.1f} ms: {dt / it * 1e6:6.1f} us per iteration, "
-              f"residual {res:.2e}")
+    loops = ("torch", "fused") if args.cg_loop == "both" else (args.cg_loop,)
+    for name, fn, prepare, dg in (
+            ("matrix-free apply", lambda v: eng._apply_p2_rows(1.0, 0.0, v),
+             lambda v, out: eng._prepared_apply(1.0, 0.0, v, out), diag),
+            ("SpMV on K", Ks.matvec, Ks._prepared_spmv, Ks.diagonal())):
+        for loop in loops:
+            solve, matvec = (conjugate_gradients, fn) if loop == "torch" else (fused_conjugate_gradients, _into(prepare))
+            solve(matvec, dg, f, free, None, 0.0, 25)  # warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _, it, res = solve(matvec, dg, f, free, None, 0.0, args.cg_iters)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print(f"  CG with {name:18s} {loop:5s} loop {it} iterations in {dt * 1e3:7.1f} ms: "
+                  f"{dt / it * 1e6:6.1f} us per iteration, residual {res:.2e}")
 
 
 def main():
@@ -111,6 +116,8 @@ def main():
     p.add_argument("--blocks", type=int, default=10)
     p.add_argument("--per-block", type=int, default=20)
     p.add_argument("--cg-iters", type=int, default=200)
+    p.add_argument("--cg-loop", choices=("torch", "fused", "both"), default="both",
+                   help="the CG loop to time: the torch operations, the tfem_cg_* launches, or one after the other")
     args = p.parse_args()
     torch.set_default_dtype(torch.float64)
     torch.set_default_device("cuda")
