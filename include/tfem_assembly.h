@@ -460,6 +460,22 @@ int tfem_p1_apply_rings_coef(const void *coords, int real_bytes, int64_t n_verts
                              double alpha, double beta, const tfem_source_program *kappa,
                              const tfem_source_program *c, const void *plan_device,
                              const int64_t *plan_layout_host, const void *u, void *y, void *stream);
+/* Y = K U of the same operator for n_vec vectors at once: U and Y (DEVICE, n_verts x n_vec reals each,
+ * ROW-major as for tfem_p1_apply_rings_multi; the plan's vertex numbering) must not overlap; every
+ * entry of Y is written once (0 for a vertex without elements).  The coefficient programs are
+ * evaluated once per row and triangle for a pass of up to 8 columns (4 with 15-slot records), a
+ * larger n_vec is served in several passes over column ranges; column j of Y is bit for bit what
+ * tfem_p1_apply_rings_coef gives for column j of U.  n_vec >= 1 of any size within the 32-bit extent (n_vec = 1 IS
+ * tfem_p1_apply_rings_coef); u == NULL is an error here (the diagonal has one column:
+ * tfem_p1_apply_rings_coef).  Refused before anything is launched, Y untouched: both programs NULL
+ * or an invalid one, overlapping U and Y (TFEM_ERR_INVALID_ARGUMENT), an extent n_verts * n_vec *
+ * real_bytes >= 2^32 (TFEM_ERR_INDEX_RANGE), plans with long rows and unknown integration orders
+ * (TFEM_ERR_UNSUPPORTED).  No allocation, no synchronisation. */
+int tfem_p1_apply_rings_coef_multi(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
+                                   double alpha, double beta, const tfem_source_program *kappa,
+                                   const tfem_source_program *c, const void *plan_device,
+                                   const int64_t *plan_layout_host, const void *u, void *y,
+                                   int64_t n_vec, void *stream);
 
 /* Multi-GPU: the rows shared with other ranks first.  create_priority = create with
  * vertex_priority_host (n_verts bytes, non-zero = flagged; NULL = none): the tiles that own a flagged

@@ -1236,17 +1236,23 @@ class AssemblyEngine:
 
     def _apply_rings_coef(self, alpha, beta, kappa, c, u, out=None):
         """One tfem_p1_apply_rings_coef launch in the ENGINE's numbering: K u of the
-        variable-coefficient form without its CSR values, u None: the diagonal."""
-        if _is_block(u):  # one launch per column (a multi-column coefficient kernel: DESIGN.md section 7)
-            u = u.to(self.device, self.dtype)
-            cols = [self._apply_rings_coef(alpha, beta, kappa, c, u[:, j]) for j in range(u.shape[1])]
-            y = torch.stack(cols, dim=1)
-            if out is not None:
-                return self._output(out, y.numel(), "operator result").copy_(y.reshape(-1)).view(y.shape)
-            return y
+        variable-coefficient form without its CSR values, u None: the diagonal.  A block (n_dofs, k),
+        k >= 2, is one tfem_p1_apply_rings_coef_multi call: the coefficient programs are evaluated once
+        per pass of columns, every column bit for bit the single launch's; result (n_dofs, k)."""
         rings = self._coef_rings()
         if rings is None:
             raise NotImplementedError("the variable-coefficient operator needs a ring plan without long rows (P1)")
+        if _is_block(u):
+            u = u.to(self.device, self.dtype).contiguous()  # row-major: a vertex's k values are consecutive
+            if u.shape[0] != self.n_dofs:
+                raise ValueError(f"apply: u has {u.shape[0]} rows, the operator {self.n_dofs} columns")
+            k = int(u.shape[1])
+            y = self._output(out, self.n_dofs * k, "operator result")
+            if y.data_ptr() == u.data_ptr():
+                raise ValueError("apply: out must not be u")
+            with torch.cuda.device(self.device):
+                self._apply_launch(alpha, beta, u, y, programs=(kappa, c), k=k)()
+            return y.view(self.n_dofs, k)
         if u is not None:
             u = u.to(self.device, self.dtype).reshape(-1).contiguous()
             if u.shape[0] != self.n_dofs:
@@ -1281,16 +1287,16 @@ class AssemblyEngine:
         """The matrix-free launch y = K u in the ENGINE's numbering with every argument converted
         ONCE (the loop of sparse.fused_conjugate_gradients applies the same two buffers every
         iteration): the returned callable only enqueues, on the stream that is current NOW.  u and
-        y: contiguous device tensors of this engine's dtype, (n_dofs,) or (n_dofs, k); P1 constant
-        coefficients take a block in one tfem_p1_apply_rings_multi call, the coefficient and the P2
-        launches go column by column through a contiguous pair of columns."""
+        y: contiguous device tensors of this engine's dtype, (n_dofs,) or (n_dofs, k); P1 takes a
+        block in one call (tfem_p1_apply_rings_multi, with `programs` tfem_p1_apply_rings_coef_multi),
+        the P2 launch goes column by column through a contiguous pair of columns."""
         for t in (u, y):
             if t.dtype != self.dtype or t.device != self.device or not t.is_contiguous() or t.shape[0] != self.n_dofs:
                 raise ValueError(f"prepared apply: contiguous {self.dtype} tensors of {self.n_dofs} rows on {self.device}")
         if u.shape != y.shape or u.data_ptr() == y.data_ptr():
             raise ValueError("prepared apply: u and y must be two tensors of one shape")
         k = int(u.shape[1]) if _is_block(u) else 1
-        multi = k > 1 and programs is None and self.poly_order == 1
+        multi = k > 1 and self.poly_order == 1
         if k > 1 and not multi:
             u_col, y_col = (torch.empty(self.n_dofs, dtype=self.dtype, device=self.device) for _ in range(2))
             one = self._prepared_apply(alpha, beta, u_col, y_col, programs)
@@ -1306,7 +1312,8 @@ class AssemblyEngine:
 
     def _apply_launch(self, alpha, beta, u, y, programs=None, k=1):
         """THE call of the matrix-free apply launches (tfem_p1_apply_rings, _multi for k >= 2,
-        _coef with `programs` = (kappa, c), tfem_p2_apply_rows on P2) with its arguments converted:
+        _coef with `programs` = (kappa, c), _coef_multi with both, tfem_p2_apply_rows on P2) with its
+        arguments converted:
         y = K u in the engine's numbering, u None: the diagonal; u and y as the callers have
         checked them.  The returned callable enqueues on the stream that is current now."""
         d = self._inputs()
@@ -1329,8 +1336,13 @@ class AssemblyEngine:
             where = (_native.ptr(plan["blob"]), c_void_p(plan["layout"].ctypes.data))
             head = (*head, self.n_dofs, self.quad_order, *scale)
             if programs is not None:
-                fn = self.lib.tfem_p1_apply_rings_coef
-                args = (*head, self._program_ref(programs[0]), self._program_ref(programs[1]), *where, *tail, stream)
+                coef = (*head, self._program_ref(programs[0]), self._program_ref(programs[1]), *where, *tail)
+                if k > 1:
+                    fn = self.lib.tfem_p1_apply_rings_coef_multi
+                    args = (*coef, k, stream)
+                else:
+                    fn = self.lib.tfem_p1_apply_rings_coef
+                    args = (*coef, stream)
             elif k > 1:
                 fn = self.lib.tfem_p1_apply_rings_multi
                 args = (*head, *where, *tail, k, stream)

@@ -17,6 +17,7 @@
 // Plans with long rows (TFEM_RING_LONG=1: vertices with 8 .. 15 neighbours listed apart): the
 // tile launch skips those rows and k_p1_apply_long_rows forms them, sixteen lanes per row as in
 // k_p1_long_rows.
+#include "tfem_rings_cols.hpp"
 #include "tfem_rings_kernel.hpp"
 
 namespace tfem {
@@ -157,55 +158,8 @@ __global__ __launch_bounds__(kRingBlock) void k_p1_apply_long_rows(const T *coor
 // Several vectors in one launch: Y = K U, U and Y (n_verts, n_vec) row-major.  The row record, the
 // coordinates, ring_row and the chain loads -> barrier -> rows -> barrier of a tile are paid once
 // for the NV columns of a pass; the lane then forms NV sums, each in the order of k_p1_apply_rows.
+// The columns are staged with tfem_rings_cols.hpp (ApplyMultiArgs, apply_load_cols, apply_store_cols).
 // ---------------------------------------------------------------------------------------
-template <typename T>
-struct ApplyMultiArgs {
-  const T *u;
-  T *y;
-  unsigned u_bytes, y_bytes;
-  unsigned n_vec;  // row stride of u and y (reals)
-  unsigned col0;   // first column of this pass
-  unsigned n_col;  // columns of this pass, 1 .. NV (the last pass of a launch may be narrower)
-};
-
-// NV consecutive reals of one row.  All NV are fetched whatever n_col is: behind the pass's last
-// column they are the head of the next row (or the zeros behind the array); those sums are formed
-// and dropped.  Doubles by 16-byte loads at 8-byte alignment (as ring_load_fq).
-template <typename T, int NV>
-__device__ __forceinline__ void apply_load_cols(ring_rsrc_t r, unsigned byte, T (&v)[NV]) {
-#pragma unroll
-  for (int c = 0; c < NV; c += 2) {
-    if constexpr (sizeof(T) == 8) {
-      const ru32x4 x = __builtin_amdgcn_raw_buffer_load_b128(r, byte + unsigned(c) * 8u, 0, 0);
-      v[c] = __builtin_bit_cast(double, ru32x2{x.x, x.y});
-      v[c + 1] = __builtin_bit_cast(double, ru32x2{x.z, x.w});
-    } else {
-      v[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte + unsigned(c) * 4u, 0, 0));
-      v[c + 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte + unsigned(c) * 4u + 4u, 0, 0));
-    }
-  }
-}
-
-// The first n_col of NV sums -> one row of Y (n_col is uniform: scalar branches).
-template <typename T, int NV>
-__device__ __forceinline__ void apply_store_cols(ring_rsrc_t r, unsigned byte, const T (&v)[NV], unsigned n_col) {
-#pragma unroll
-  for (int c = 0; c < NV; c += 2) {
-    if constexpr (sizeof(T) == 8) {
-      const ru32x2 x = __builtin_bit_cast(ru32x2, v[c]), y = __builtin_bit_cast(ru32x2, v[c + 1]);
-      if (unsigned(c + 1) < n_col)
-        __builtin_amdgcn_raw_buffer_store_b128(ru32x4{x.x, x.y, y.x, y.y}, r, byte + unsigned(c) * 8u, 0, 0);
-      else if (unsigned(c) < n_col)
-        __builtin_amdgcn_raw_buffer_store_b64(x, r, byte + unsigned(c) * 8u, 0, 0);
-    } else {
-      if (unsigned(c) < n_col)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[c]), r, byte + unsigned(c) * 4u, 0, 0);
-      if (unsigned(c + 1) < n_col)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[c + 1]), r, byte + unsigned(c) * 4u + 4u, 0, 0);
-    }
-  }
-}
-
 // k_p1_apply_rows for NV columns per pass.  LDS: the coordinates, then NV reals per local vertex
 // (us[NV * lv + c]: a vertex's values are one 16-byte-aligned piece, read with the widest LDS loads).
 template <typename T, int SLOTS, bool MASS, bool CHUNK, int NV>

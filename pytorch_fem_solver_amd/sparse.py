@@ -477,9 +477,10 @@ class FormOperator:
     wraps the CSRMatrix of today's assembly and applies it with tfem_csr_spmv (P2, fractures, any
     other integrand, meshes without a ring plan); the interface and the results are the same.
     Vectors are taken and returned in the caller's DoF numbering, of shape (N,) or (N, 1); a block
-    (N, k) of k >= 2 vectors gives (N, k): matrix-free with constant coefficients by ONE
-    tfem_p1_apply_rings_multi call that forms the rows of K once for the k columns, every other
-    operator by its single-vector launch once per column.
+    (N, k) of k >= 2 vectors gives (N, k): matrix-free on P1 by ONE call that forms the rows of K
+    once for the k columns (tfem_p1_apply_rings_multi; with coefficient programs
+    tfem_p1_apply_rings_coef_multi, which evaluates the programs once for the k columns), every
+    other operator by its single-vector launch once per column.
 
     ``layout="matrix_free"`` is the strict request: the plan is built at the call, the operator it
     returns is matrix-free from the start (``matrix_free`` True), and a basis or form without the
