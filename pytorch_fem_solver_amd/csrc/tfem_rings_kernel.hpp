@@ -69,6 +69,10 @@ struct RingArgs {
   SrcProgram<T> src;  // SRC instantiations: f(x, y), evaluated at the integration points in the launch
 };
 
+static_assert(__builtin_offsetof(RingArgs<double>, hw) == __builtin_offsetof(RingArgs<double>, lam) + 3 * kMaxQuad * sizeof(double) &&
+                  __builtin_offsetof(RingArgs<float>, hw) == __builtin_offsetof(RingArgs<float>, lam) + 3 * kMaxQuad * sizeof(float),
+              "the kernels read hw through the pointer to lam");
+
 constexpr int kRingBand = 11;  // short slot loop of the 15-slot kernels (0: none)
 // Issue priority of the source-program launches: workgroup b takes turns with the others by
 // (tile number + b >> kRingPrioShift) & 3 (the kernel's tile loop)
@@ -764,33 +768,68 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
 #pragma unroll
     for (int j = 0; j < kNE; ++j) codes[j] = tv[SRC ? j : 0];
     T fv[kNE * (QL > 0 ? QL : 1)];
-    src_run_wide<T, (QL > 0 ? QL : 1), kNE>(prog, xyc, codes, a.lam, fv);
+    // where the elements' vertices sit in LDS: formed once, for both coordinate pushes and the
+    // determinants (3 kNE registers)
+    const T *vert_at[kNE][3];
+#pragma unroll
+    for (int j = 0; j < kNE; ++j)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) vert_at[j][i] = xyc + 2 * __builtin_amdgcn_ubfe(codes[j], 10 * i, 10);
+    src_run_wide<T, (QL > 0 ? QL : 1), kNE>(prog, vert_at, a.lam, __builtin_offsetof(RingArgs<T>, lam), fv);
+    // the constants of the shares; fp64: scalar loads in flight during the determinants' LDS reads
+    // (src_kernarg_table: not carried through the interpreter in spill lanes)
+    constexpr int kQ = QL > 0 ? QL : 1;
+    T qs[3], hwq[kQ], lamq[3][kQ];
+    if constexpr (QL == 4) {
+      if constexpr (kSrcTableLoads<T>) {
+        const src_const_tab<T> t = src_kernarg_table<T>(__builtin_offsetof(RingArgs<T>, qsym));
+#pragma unroll
+        for (int i = 0; i < 3; ++i) qs[i] = t[3 + i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) qs[i] = a.qsym[3 + i];
+      }
+    } else if constexpr (kSrcTableLoads<T>) {
+      const src_const_tab<T> tl = src_kernarg_table<T>(__builtin_offsetof(RingArgs<T>, lam));
+      const src_const_tab<T> th = tl + 3 * kMaxQuad;  // RingArgs::hw follows lam: one opaque pointer
+#pragma unroll
+      for (int q = 0; q < kQ; ++q) {
+        hwq[q] = th[q];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) lamq[i][q] = tl[i * kMaxQuad + q];
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < kQ; ++q) {
+        hwq[q] = a.hw[q];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) lamq[i][q] = a.lam[i][q];
+      }
+    }
 #pragma unroll
     for (int j = 0; j < kNE; ++j) {
       const int l = vtid + j * kRingBlock;
       if (l < d.n_tv) {
         const unsigned code = codes[j];
-        T x0, y0, x1, y1, x2, y2;
-        lds_xy(xyc, code & 0x3FFu, x0, y0);
-        lds_xy(xyc, (code >> 10) & 0x3FFu, x1, y1);
-        lds_xy(xyc, (code >> 20) & 0x3FFu, x2, y2);
+        const T x0 = vert_at[j][0][0], y0 = vert_at[j][0][1], x1 = vert_at[j][1][0], y1 = vert_at[j][1][1],
+                x2 = vert_at[j][2][0], y2 = vert_at[j][2][1];
         const T det = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0);
         if constexpr (QL == 4) {
           // the order-3 rule's structure (RingArgs::qsym): 7 operations instead of 16
           const T *f4 = fv + j * 4;
-          const T base = src_fma<T>(a.qsym[3], f4[0], a.qsym[4] * ((f4[1] + f4[2]) + f4[3]));
-          add_share(code & 0x3FFu, acc, det * src_fma<T>(a.qsym[5], f4[3], base));
-          add_share((code >> 10) & 0x3FFu, acc, det * src_fma<T>(a.qsym[5], f4[1], base));
-          add_share((code >> 20) & 0x3FFu, acc, det * src_fma<T>(a.qsym[5], f4[2], base));
+          const T base = src_fma<T>(qs[0], f4[0], qs[1] * ((f4[1] + f4[2]) + f4[3]));
+          add_share(code & 0x3FFu, acc, det * src_fma<T>(qs[2], f4[3], base));
+          add_share((code >> 10) & 0x3FFu, acc, det * src_fma<T>(qs[2], f4[1], base));
+          add_share((code >> 20) & 0x3FFu, acc, det * src_fma<T>(qs[2], f4[2], base));
         } else {
           T fw[QL > 0 ? QL : 1];
 #pragma unroll
-          for (int q = 0; q < QL; ++q) fw[q] = fv[j * (QL > 0 ? QL : 1) + q] * a.hw[q];
+          for (int q = 0; q < QL; ++q) fw[q] = fv[j * (QL > 0 ? QL : 1) + q] * hwq[q];
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
             T g = T(0);
 #pragma unroll
-            for (int q = 0; q < QL; ++q) g = g + fw[q] * a.lam[i][q];
+            for (int q = 0; q < QL; ++q) g = g + fw[q] * lamq[i][q];
             add_share((code >> (10 * i)) & 0x3FFu, acc, det * g);
           }
         }
@@ -833,6 +872,9 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
         lds_xy(xyc, (code >> 10) & 0x3FFu, x1, y1);
         lds_xy(xyc, (code >> 20) & 0x3FFu, x2, y2);
         T xq[QL > 0 ? QL : 1], yq[QL > 0 ? QL : 1], fv[QL > 0 ? QL : 1];
+        // (the tables stay the by-value argument's here: read by scalar loads like the wide pass reads
+        // them, 100 -> 34 spilled scalars, but hipcc then leaves fourteen of these instantiations a
+        // private segment of 36 bytes that no instruction touches -- profiles/fused_hot_loop.log)
 #pragma unroll
         for (int q = 0; q < QL; ++q) {
           xq[q] = (a.lam[0][q] * x0 + a.lam[1][q] * x1) + a.lam[2][q] * x2;

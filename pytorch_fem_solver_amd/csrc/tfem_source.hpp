@@ -237,6 +237,31 @@ __device__ __forceinline__ src_const_ptr<T> src_in_kernarg(size_t offset) {
   return (src_const_ptr<T>)((kbytes)__builtin_amdgcn_kernarg_segment_ptr() + offset);
 }
 
+// A table of the launch structure (values of T at byte `offset` of the kernel-argument segment),
+// read by scalar loads WHERE IT IS USED.  Taken from the by-value argument, a table
+// that is read inside the tile loop sits in scalar registers for the whole kernel; the fused
+// launches have more such values than scalar registers, the rest lives in lanes of a VGPR and
+// every use costs a v_readlane -- a vector instruction, in kernels bound by vector issue (26 of
+// the 78 vector instructions of a coordinate push were such reloads).  The empty asm makes the
+// address opaque, so that the loads stay where they are written and are not hoisted back out of
+// the loop; the kernel-argument segment sits in the scalar cache.
+template <typename T>
+using src_const_tab = const T __attribute__((address_space(4))) *;
+
+// fp64 launches only: the float instantiations have half the table in scalar registers and spill
+// little of it, and with the loads hipcc left five of them a private segment of 20 or 36 bytes that no
+// instruction touches (the slot of a spilled register tuple, dead after the spill went to lanes).
+template <typename T>
+constexpr bool kSrcTableLoads = sizeof(T) == 8;
+
+template <typename T>
+__device__ __forceinline__ src_const_tab<T> src_kernarg_table(size_t offset) {
+  typedef const char __attribute__((address_space(4))) *kbytes;
+  kbytes base = (kbytes)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(base));  // the segment's own pointer: `offset` becomes the loads' immediate
+  return (src_const_tab<T>)(base + offset);
+}
+
 // The program as every wave keeps it while the kernel runs: lane i holds operation i and its
 // constant (3 VGPRs).  The interpreter fetches operation pc with v_readlane -- a few cycles --
 // instead of scalar loads from the kernel-argument segment, whose latency (two dependent loads
@@ -370,10 +395,14 @@ __device__ __forceinline__ void src_run(const SrcLanes<T> &prog, const T (&x)[QL
 // moves) costs about as much as four fp64 additions on QL = 4 values, and with one element per
 // pass it was 40 % of the time of a sin * sin source.  Two entries of 12 doubles take the
 // registers four entries of 4 plus the points took; the coordinates of the elements' vertices
-// are read from LDS (`xyc`, tile-local ids in `codes`) when a PUSH needs them, not kept.
+// are read from LDS (`vert_at`: where the (x, y) of vertex k of element e sits) when a PUSH needs
+// them, not kept.
+// `lam_arg`: the launch structure's table l_i(q); `lam_offset`: where it sits in the kernel-argument
+// segment -- a PUSH of an fp64 launch reads it from there (src_kernarg_table, kSrcTableLoads).
 template <typename T, int QL, int NE>
-__device__ __forceinline__ void src_run_wide(const SrcLanes<T> &prog, const T *xyc, const unsigned (&codes)[NE],
-                                             const T (&lam)[3][kMaxQuad], T (&out)[NE * QL]) {
+__device__ __forceinline__ void src_run_wide(const SrcLanes<T> &prog, const T *const (&vert_at)[NE][3],
+                                             const T (&lam_arg)[3][kMaxQuad], size_t lam_offset,
+                                             T (&out)[NE * QL]) {
   constexpr int N = NE * QL;
   // no zero fill: a valid program (src_validate) writes an entry before it reads it; the empty
   // asm gives the registers a defined value without an instruction
@@ -404,35 +433,36 @@ __device__ __forceinline__ void src_run_wide(const SrcLanes<T> &prog, const T *x
       depth = __builtin_amdgcn_readfirstlane(depth - 1);  // the two-operand operations leave one entry
     }
     switch (op) {
-      case TFEM_SRC_PUSH_X:
-      case TFEM_SRC_PUSH_Y: {
-        const int comp = op == TFEM_SRC_PUSH_Y ? 1 : 0;  // wave-uniform
-        // the LDS addresses are formed here, from the packed ids: formed once in front of the
-        // program loop they cost nine registers the kernel does not have (they went to scratch:
-        // +45 MB of writes per launch at 1e7 elements).  All reads are issued before the first use.
-        // (The points keep the reference's form l^T X, basis.py:90-91: the 4-point rule's structure --
-        // b S + d X_i -- would save nine operations per element, but sin(pi x) at the boundary x -> 1
-        // amplifies a last-bit difference of x_q by 1 / (1 - x) ~ 1e4, and the load vector's entries
-        // there left the 1e-12 entry-wise bound against the oracle: 2e-12 at 1e7 elements.)
-        unsigned code[NE];
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-          code[e] = codes[e];
-          asm volatile("" : "+v"(code[e]));
-        }
-        T vert[NE][3];
-#pragma unroll
-        for (int e = 0; e < NE; ++e)
-#pragma unroll
-          for (int k = 0; k < 3; ++k)  // one bit-field extract + one shift-add per vertex
-            vert[e][k] = xyc[2 * __builtin_amdgcn_ubfe(code[e], 10 * k, 10) + comp];
-#pragma unroll
-        for (int e = 0; e < NE; ++e)
-#pragma unroll
-          for (int q = 0; q < QL; ++q)  // fused multiply-adds (the file is compiled without contraction)
-            s0[e * QL + q] = c * src_fma<T>(lam[2][q], vert[e][2], src_fma<T>(lam[1][q], vert[e][1], lam[0][q] * vert[e][0]));
-        break;
-      }
+      // The two coordinate pushes are separate cases: the component is then the LDS reads' immediate
+      // offset, on addresses the caller formed once per pass (`vert_at`).  All reads are issued before
+      // the first use.
+      // (The points keep the reference's form l^T X, basis.py:90-91: the 4-point rule's structure --
+      // b S + d X_i -- would save nine operations per element, but sin(pi x) at the boundary x -> 1
+      // amplifies a last-bit difference of x_q by 1 / (1 - x) ~ 1e4, and the load vector's entries
+      // there left the 1e-12 entry-wise bound against the oracle: 2e-12 at 1e7 elements.)
+      // The table first: one batch of scalar loads per push, in flight while the LDS reads run.
+#define TFEM_SRC_PUSH_COORD(comp)                                                                    \
+  {                                                                                                  \
+    T lam[3][QL];                                                                                    \
+    if constexpr (kSrcTableLoads<T>) {                                                               \
+      const src_const_tab<T> ltab = src_kernarg_table<T>(lam_offset);                                \
+      _Pragma("unroll") for (int k = 0; k < 3; ++k)                                                  \
+        _Pragma("unroll") for (int q = 0; q < QL; ++q) lam[k][q] = ltab[k * kMaxQuad + q];           \
+    } else {                                                                                         \
+      _Pragma("unroll") for (int k = 0; k < 3; ++k)                                                  \
+        _Pragma("unroll") for (int q = 0; q < QL; ++q) lam[k][q] = lam_arg[k][q];                    \
+    }                                                                                                \
+    T vert[NE][3];                                                                                   \
+    _Pragma("unroll") for (int e = 0; e < NE; ++e)                                                   \
+      _Pragma("unroll") for (int k = 0; k < 3; ++k) vert[e][k] = vert_at[e][k][comp];                \
+    _Pragma("unroll") for (int e = 0; e < NE; ++e)                                                   \
+      _Pragma("unroll") for (int q = 0; q < QL; ++q) /* fused multiply-adds (no contraction here) */ \
+        s0[e * QL + q] =                                                                             \
+            c * src_fma<T>(lam[2][q], vert[e][2], src_fma<T>(lam[1][q], vert[e][1], lam[0][q] * vert[e][0])); \
+  }
+      case TFEM_SRC_PUSH_X: TFEM_SRC_PUSH_COORD(0) break;
+      case TFEM_SRC_PUSH_Y: TFEM_SRC_PUSH_COORD(1) break;
+#undef TFEM_SRC_PUSH_COORD
       case TFEM_SRC_PUSH_C: TFEM_SRC_SET(c) break;
       case TFEM_SRC_ADD: TFEM_SRC_SET(l + t) break;
       case TFEM_SRC_SUB: TFEM_SRC_SET(l - t) break;
