@@ -477,6 +477,54 @@ int tfem_p1_apply_rings_coef_multi(const void *coords, int real_bytes, int64_t n
                                    const int64_t *plan_layout_host, const void *u, void *y,
                                    int64_t n_vec, void *stream);
 
+/* Coefficient DATA: the CSR values of
+ *   alpha * int kappa grad u . grad v + beta * int c u v
+ * over a ring plan, kappa and c given as values at the integration points (replaces
+ * abstract_basis.py:74-93 applied to a caller's `kq * (v_grad @ v_grad.mT) + cq * (v @ v.mT)` with
+ * tensors kq, cq, whose (n_elems, Q, 3, 3) integrand the reference builds with torch).
+ *   kappa / c: DEVICE, n_elems * kappa_nq (c_nq) reals, element-major in the element order of the
+ *   connectivity the plan was built from, the q order of tfem_quadrature_rule; *_nq = Q (a value per
+ *   integration point) or 1 (one value per element, read once per element and never expanded);
+ *   NULL = the constant 1 (its *_nq is ignored); both NULL: TFEM_ERR_INVALID_ARGUMENT
+ *   (tfem_p1_assemble_rings / tfem_p1_apply_rings are the entry points then).
+ * One launch: per tile the values of the tile's elements (the plan's tile_elems, layout[16], as a
+ * list or as runs) are read once, coalesced, and reduced to one number per element for the stiffness
+ * term and six for the mass term, which the rows pick up from LDS through their slot codes
+ * (row_ecodes, layout[15]) -- the lookup of the fused load vector; no atomics.  vals (DEVICE): the
+ * values of the CSR pattern the plan was built from, bounds-checked against layout[1] * layout[5]
+ * reals as for tfem_p1_rings_coef.  K_ij and K_ji agree to rounding, not bit for bit.
+ * Refused before anything is launched, the outputs untouched: real_bytes not 4 or 8, a NULL layout,
+ * negative sizes, *_nq neither 1 nor Q, both fields NULL, u overlapping y
+ * (TFEM_ERR_INVALID_ARGUMENT); an extent of 2^32 bytes or more, n_elems * *_nq * real_bytes
+ * included (TFEM_ERR_INDEX_RANGE); plans with long rows (layout[23] > 0), plans whose tiles do not
+ * fit the element stage (layout[18] == 0), plans whose largest tile (layout[3] vertices, layout[17]
+ * elements) needs more than 64 KB of LDS, unknown integration orders (TFEM_ERR_UNSUPPORTED).  Empty
+ * plans succeed and launch nothing.  No allocation, no synchronisation. */
+int tfem_p1_rings_field(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
+                        double alpha, double beta, const void *kappa, int kappa_nq, const void *c,
+                        int c_nq, int64_t n_elems, const void *plan_device,
+                        const int64_t *plan_layout_host, void *vals, void *stream);
+/* The same operator applied: y[n_verts] = K u without the CSR values (abstract_basis.py:74-93, applied
+ * instead of stored); u == NULL: y = diag(K).  u and y as for tfem_p1_apply_rings; they must not
+ * overlap. */
+int tfem_p1_apply_rings_field(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
+                              double alpha, double beta, const void *kappa, int kappa_nq,
+                              const void *c, int c_nq, int64_t n_elems, const void *plan_device,
+                              const int64_t *plan_layout_host, const void *u, void *y, void *stream);
+/* The derivative of sum_cols g^T K u with respect to the values (the backward of the apply launch in
+ * kappa and c; abstract_basis.py:74-93 differentiated in the coefficient of the integrand), element
+ * form, one lane per element:
+ *   grad_kappa[e][q] = alpha * dx_q * sum_cols grad g_h . grad u_h
+ *   grad_c[e][q]     = beta  * dx_q * sum_cols g_h(x_q) u_h(x_q),   dx_q = (w_q / 2) * det_e
+ * with the reference's signed determinant (element_tri.py:139).  conn: (n_elems, 3) int32 vertex ids
+ * (DEVICE) in the numbering of coords, g and u; g, u: n_verts x n_vec reals, ROW-major as for
+ * tfem_p1_apply_rings_multi (n_vec >= 1).  grad_kappa / grad_c: (n_elems, Q) reals, either may be
+ * NULL (both: nothing is launched); every entry is written once, no atomics.  Data with one value
+ * per element takes the sum of its row. */
+int tfem_p1_field_adjoint(const void *coords, int real_bytes, const void *conn, int64_t n_elems,
+                          int64_t n_verts, int quad_order, double alpha, double beta, const void *g,
+                          const void *u, int64_t n_vec, void *grad_kappa, void *grad_c, void *stream);
+
 /* Multi-GPU: the rows shared with other ranks first.  create_priority = create with
  * vertex_priority_host (n_verts bytes, non-zero = flagged; NULL = none): the tiles that own a flagged
  * vertex come first in the plan's tile list (*n_priority_tiles of them), the order inside both groups

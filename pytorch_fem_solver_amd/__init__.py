@@ -17,6 +17,7 @@ from .basis import (
 from .element import AbstractElement, ElementLine, ElementTri
 from .mesh import AbstractMesh, FracturesTri, MeshData, MeshesTri, MeshTri
 from .sparse import CSRMatrix, FormOperator
+from .basis.forms import CoefficientField
 
 __all__ = [
     "Basis",
@@ -30,5 +31,6 @@ __all__ = [
     "MeshesTri",
     "CSRMatrix",
     "FormOperator",
+    "CoefficientField",
     "meshgen",
 ]

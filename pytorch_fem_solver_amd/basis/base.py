@@ -103,6 +103,14 @@ class _ResidualFormFunction(torch.autograd.Function):
         return g_coefficient, g_flux, None, None, None
 
 
+#: what a stored operator says to an integrand (or coefficient data) that carries autograd history
+_NOT_DIFFERENTIABLE = (
+    "integrate_bilinear_form: the integrand carries autograd history, but the "
+    "assembled operator is written by the HIP kernels and is not differentiable; "
+    "detach() the integrand, or differentiate a linear form / functional instead"
+)
+
+
 class AbstractBasis(abc.ABC):
     """Finite-element basis on a mesh (abstract_basis.py:10-40)."""
 
@@ -167,6 +175,14 @@ class AbstractBasis(abc.ABC):
         ...
 
     # ---- integration API ---------------------------------------------------------------
+    def coefficient(self, values):
+        """Mark ``values`` as a coefficient field of this basis (``forms.CoefficientField``): values at
+        the integration points, ``(E, Q, 1, 1)`` or ``(E, Q)``, or one per element, ``(E, 1, 1, 1)``,
+        ``(E, 1)`` or ``(E,)``.  ``field * (v_grad @ v_grad.mT) + field * (v @ v.mT)`` in a bilinear
+        form is then assembled, applied and differentiated in the values by the coefficient-data
+        launches on a P1 basis; anywhere else the field is the tensor ``(E, Q | 1, 1, 1)``."""
+        return forms.CoefficientField(self, values)
+
     def integrate_functional(self, function, *args, **kwargs):
         """Per-element integral of ``function(basis, ...)`` (abstract_basis.py:65-72);
         differentiable in the integrand."""
@@ -184,7 +200,8 @@ class AbstractBasis(abc.ABC):
         (``FormOperator``: to apply and solve with; matrix-free for ``alpha * v_grad @ v_grad.mT +
         beta * v @ v.mT`` on a P1 basis with a ring plan -- also with coefficients ``kappa(x, y)``,
         ``c(x, y)`` written as expressions of the integration points' columns in front of the two
-        terms -- the assembled CSR otherwise), "matrix_free" (a ``FormOperator`` that never stores K,
+        terms, or with coefficient DATA ``basis.coefficient(values)`` there -- the assembled CSR
+        otherwise), "matrix_free" (a ``FormOperator`` that never stores K,
         decided here: what "operator" serves matrix-free on P1, and the same form on a P2 basis over
         its row plan; NotImplementedError naming the reason where no such launch applies) or None =
         dense while it fits ``DENSE_LIMIT_BYTES``, CSR beyond.
@@ -196,7 +213,7 @@ class AbstractBasis(abc.ABC):
         if layout == "matrix_free":
             return self._matrix_free_operator(expr)
         if isinstance(expr, forms.BilinearExpr) and expr.has_coefficients:
-            out = self._coefficient_form(expr, layout)
+            out = self._field_form(expr, layout) if expr.has_data else self._coefficient_form(expr, layout)
             if out is not None:
                 return out
             expr = forms.materialize(expr)  # no launch for it on this basis: the integrand, with torch
@@ -246,6 +263,11 @@ class AbstractBasis(abc.ABC):
             if engine.kernel not in ("auto", "rings"):
                 refuse(f"TFEM_KERNEL={engine.kernel} selects a path without the ring plan")
             refuse("the DoFs of this P1 basis are not the mesh's vertices: no ring plan")
+        if expr.has_coefficients and expr.has_data:
+            why = engine.field_refusal(beta, "apply")
+            if why is not None:
+                refuse(f"coefficient data: {why}")
+            return self._field_operator(expr)
         if expr.has_coefficients:
             if not engine.supports_source():
                 refuse("this basis takes no source programs for the coefficient fields")
@@ -271,11 +293,7 @@ class AbstractBasis(abc.ABC):
     def _reduce_integrand(self, integrand):
         """CSR values of a materialised bilinear integrand: the generic reduce + scatter kernels."""
         if integrand.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError(
-                "integrate_bilinear_form: the integrand carries autograd history, but the "
-                "assembled operator is written by the HIP kernels and is not differentiable; "
-                "detach() the integrand, or differentiate a linear form / functional instead"
-            )
+            raise NotImplementedError(_NOT_DIFFERENTIABLE)
         return self._engine.reduce_bilinear(integrand, self._dx)
 
     def _coefficient_programs(self, expr):
@@ -318,6 +336,59 @@ class AbstractBasis(abc.ABC):
         if programs is None:
             return None
         return self._finish_matrix(engine.bilinear_coef(alpha, beta, *programs), layout)
+
+    # ---- coefficient data (forms.CoefficientField) ---------------------------------------
+    def _field_data(self, expr):
+        """((kappa, c) values (E, Q | 1) on the engine's device, None: the constant 1; the tensors of
+        the marked fields, for autograd).  A coefficient PROGRAM on the other term becomes values once
+        (tfem_source_eval; torch where it does not fit a program)."""
+        engine = self._engine
+        values, sources = [], []
+        for field in (expr.kappa, expr.c):
+            value = source = None
+            if isinstance(field, forms.CoefficientField):
+                source = field.tensor
+                value = source.detach().to(engine.device, engine.dtype).reshape(engine.n_elems, -1).contiguous()
+            elif field is not None:
+                program = self._source_program(field)
+                if program is not None:
+                    value = engine.source_values(program)
+                else:
+                    value = self._source_values(field.materialize()).to(engine.device, engine.dtype).contiguous()
+            values.append(value)
+            sources.append(source)
+        return tuple(values), tuple(sources)
+
+    def _field_operator(self, expr):
+        """The matrix-free operator of a form with coefficient data (the caller has checked that the
+        apply launch takes this basis)."""
+        engine, alpha, beta = self._engine, expr.alpha, expr.beta
+        fields, sources = self._field_data(expr)
+
+        def assemble():
+            vals = engine.bilinear_field(alpha, beta, fields)
+            if vals is None:  # no store launch for this plan: the integrand, with torch
+                with torch.no_grad():
+                    vals = self._reduce_integrand(forms.materialize(expr))
+            return engine.wrap_csr_home(vals)
+
+        return FormOperator(engine.n_dofs, engine.dtype, engine.home, assemble, engine=engine, alpha=alpha,
+                            beta=beta, fields=fields, field_sources=sources, matrix_free=True)
+
+    def _field_form(self, expr, layout):
+        """``alpha * kappa * stiffness + beta * c * mass`` with coefficient DATA through the data
+        launches (tfem_p1_rings_field / tfem_p1_apply_rings_field), or None when they do not apply."""
+        engine = self._engine
+        if layout == "operator":
+            if engine.field_refusal(expr.beta, "apply") is not None:
+                return None
+            return self._field_operator(expr)
+        if engine.field_refusal(expr.beta, "store") is not None:
+            return None
+        fields, sources = self._field_data(expr)
+        if torch.is_grad_enabled() and any(s is not None and s.requires_grad for s in sources):
+            raise NotImplementedError(_NOT_DIFFERENTIABLE)
+        return self._finish_matrix(engine.bilinear_field(expr.alpha, expr.beta, fields), layout)
 
     def assemble_system(self, bilinear, linear, *args, layout=None, **kwargs):
         """``(integrate_bilinear_form(bilinear, ...), integrate_linear_form(linear, ...))`` -- the

@@ -1283,23 +1283,161 @@ class AssemblyEngine:
         """diag(K) of the variable-coefficient form in the caller's numbering."""
         return self._dofs_out(self._apply_rings_coef(alpha, beta, kappa, c, None))
 
-    def _prepared_apply(self, alpha, beta, u, y, programs=None):
+    # ------------------------------------------------------------------ coefficient data
+    #: LDS a launch over a ring plan may ask for (csrc/tfem_rings_field.hip refuses above it)
+    FIELD_LDS_LIMIT = 64 * 1024
+
+    def field_refusal(self, beta, mode):
+        """Why the coefficient-data launches (csrc/tfem_rings_field.hip) do not take this basis, or
+        None when they do: P1 on one mesh with a ring plan (kernel "auto" / "rings") without long
+        rows, whose tiles fit the element stage and, for the launch's ``mode`` ("apply", "diag",
+        "store") with or without a mass term, 64 KB of LDS -- the launch's own refusals, known here
+        before anything is launched."""
+        if not self.may_apply_matrix_free():
+            if self.kernel not in ("auto", "rings"):
+                return f"TFEM_KERNEL={self.kernel} selects a path without the ring plan"
+            return "no ring plan for this basis (P1 on one mesh, DoFs = vertices)"
+        try:
+            rings = self.ring_plan()
+        except NotImplementedError:
+            rings = None
+        if rings is None:
+            return "the fans of this P1 mesh have no ring form: no ring plan"
+        z = [int(v) for v in rings["layout"]]
+        if z[23] > 0:
+            return "the ring plan has long rows"
+        if z[18] == 0:
+            return "a tile of the ring plan has more elements than the launch stages"
+        rb = self.real_bytes
+        if max(z[1] * z[5], self.n_elems * self.n_quad, 2 * self.n_dofs) * rb >= 1 << 32:
+            return "an array beyond the launch's 32-bit extents"
+        stage = 4 * (64 * (z[6] + 1) + 2) if mode == "store" else 0
+        lds = rb * ((3 if mode == "apply" else 2) * ((z[3] + 1) & ~1) + stage + (7 if beta != 0.0 else 1) * max(z[17], 1))
+        if lds > self.FIELD_LDS_LIMIT:
+            return f"the {mode} launch needs {lds} bytes of LDS for this plan, more than {self.FIELD_LDS_LIMIT}"
+        return None
+
+    def _field_args(self, fields):
+        """(kappa, kappa_nq, c, c_nq, n_elems) of the data launches from (E, Q | 1) value tensors."""
+        out = []
+        for values in fields:
+            if values is not None:
+                if (values.dtype != self.dtype or values.device != self.device or not values.is_contiguous()
+                        or values.dim() != 2 or values.shape[0] != self.n_elems):
+                    raise ValueError(f"coefficient data: contiguous {self.dtype} values ({self.n_elems}, Q | 1) on {self.device}")
+            out += [_native.ptr(values), 0 if values is None else int(values.shape[1])]
+        return (*out, self.n_elems)
+
+    def bilinear_field(self, alpha, beta, fields, out=None):
+        """CSR values of alpha * int kappa grad u . grad v + beta * int c u v, kappa / c values (E, Q)
+        or (E, 1) (None: the constant 1), in ONE tfem_p1_rings_field launch; None when the launch
+        does not take this basis (the caller materialises the integrand)."""
+        if self.field_refusal(beta, "store") is not None:
+            return None
+        rings = self.ring_plan()
+        d = self._inputs()
+        nnz = int(self.csr_structure()[1].shape[0])
+        vals = self._output(out, nnz, "CSR values")
+        with torch.cuda.device(self.device):
+            _native.check(
+                self.lib.tfem_p1_rings_field(
+                    _native.ptr(d["coords"]), self.real_bytes, self.n_dofs, self.quad_order, float(alpha),
+                    float(beta), *self._field_args(fields), _native.ptr(rings["blob"]),
+                    c_void_p(rings["layout"].ctypes.data), _native.ptr(vals), self._stream(),
+                )
+            )
+        return vals
+
+    def _apply_rings_field(self, alpha, beta, fields, u, out=None):
+        """One tfem_p1_apply_rings_field launch in the ENGINE's numbering: K u of the form with
+        coefficient data without its CSR values, u None: the diagonal.  A block (n_dofs, k), k >= 2,
+        goes column by column (the same launch per column), result (n_dofs, k)."""
+        why = self.field_refusal(beta, "apply" if u is not None else "diag")
+        if why is not None:
+            raise NotImplementedError(f"the coefficient-data operator: {why}")
+        if _is_block(u):
+            u = u.to(self.device, self.dtype)
+            if u.shape[0] != self.n_dofs:
+                raise ValueError(f"apply: u has {u.shape[0]} rows, the operator {self.n_dofs} columns")
+            k = int(u.shape[1])
+            y = self._output(out, self.n_dofs * k, "operator result").view(self.n_dofs, k)
+            for j in range(k):
+                y[:, j] = self._apply_rings_field(alpha, beta, fields, u[:, j])
+            return y
+        if u is not None:
+            u = u.to(self.device, self.dtype).reshape(-1).contiguous()
+            if u.shape[0] != self.n_dofs:
+                raise ValueError(f"apply: u has {u.shape[0]} entries, the operator {self.n_dofs} columns")
+        y = self._output(out, self.n_dofs, "operator result")
+        if u is not None and y.data_ptr() == u.data_ptr():
+            raise ValueError("apply: out must not be u")
+        with torch.cuda.device(self.device):
+            self._apply_launch(alpha, beta, u, y, fields=fields)()
+        return y
+
+    def apply_field(self, alpha, beta, fields, u, out=None):
+        """K u of the form with coefficient data, matrix-free; u and the result in the caller's
+        numbering (the values are per element, in the caller's element order: the engine's
+        renumbering permutes vertices only)."""
+        if self._perm is None:
+            return self._apply_rings_field(alpha, beta, fields, u, out)
+        u_in = self._dofs_in(u.to(self.device) if _is_block(u) else u.to(self.device).reshape(-1))
+        y = self._dofs_out(self._apply_rings_field(alpha, beta, fields, u_in))
+        if out is not None:
+            return self._output(out, y.numel(), "operator result").copy_(y.reshape(-1)).view(y.shape)
+        return y
+
+    def operator_diagonal_field(self, alpha, beta, fields):
+        """diag(K) of the form with coefficient data in the caller's numbering."""
+        return self._dofs_out(self._apply_rings_field(alpha, beta, fields, None))
+
+    def field_adjoint(self, alpha, beta, g, u, want_kappa=True, want_c=True):
+        """The derivative of sum_cols g^T K u with respect to the coefficient values: (grad_kappa,
+        grad_c), each (E, Q) or None, from ONE tfem_p1_field_adjoint call.  g and u: (N,), (N, 1) or
+        (N, k) in the caller's numbering."""
+        d = self._inputs()
+
+        def inward(v):
+            v = v.detach().to(self.device, self.dtype)
+            v = v if _is_block(v) else v.reshape(-1, 1)
+            if v.shape[0] != self.n_dofs:
+                raise ValueError(f"field_adjoint: {v.shape[0]} rows, the operator has {self.n_dofs}")
+            return self._dofs_in(v).contiguous()
+
+        g, u = inward(g), inward(u)
+        if g.shape != u.shape:
+            raise ValueError("field_adjoint: g and u must have one shape")
+        shape = (self.n_elems, self.n_quad)
+        grad_kappa = torch.empty(shape, dtype=self.dtype, device=self.device) if want_kappa else None
+        grad_c = torch.empty(shape, dtype=self.dtype, device=self.device) if want_c else None
+        with torch.cuda.device(self.device):
+            _native.check(
+                self.lib.tfem_p1_field_adjoint(
+                    _native.ptr(d["coords"]), self.real_bytes, _native.ptr(d["conn_geo"]), self.n_elems,
+                    self.n_dofs, self.quad_order, float(alpha), float(beta), _native.ptr(g), _native.ptr(u),
+                    int(g.shape[1]), _native.ptr(grad_kappa), _native.ptr(grad_c), self._stream(),
+                )
+            )
+        return grad_kappa, grad_c
+
+    def _prepared_apply(self, alpha, beta, u, y, programs=None, fields=None):
         """The matrix-free launch y = K u in the ENGINE's numbering with every argument converted
         ONCE (the loop of sparse.fused_conjugate_gradients applies the same two buffers every
         iteration): the returned callable only enqueues, on the stream that is current NOW.  u and
         y: contiguous device tensors of this engine's dtype, (n_dofs,) or (n_dofs, k); P1 takes a
         block in one call (tfem_p1_apply_rings_multi, with `programs` tfem_p1_apply_rings_coef_multi),
-        the P2 launch goes column by column through a contiguous pair of columns."""
+        the P2 launch and the coefficient-data launch (`fields`) go column by column through a
+        contiguous pair of columns."""
         for t in (u, y):
             if t.dtype != self.dtype or t.device != self.device or not t.is_contiguous() or t.shape[0] != self.n_dofs:
                 raise ValueError(f"prepared apply: contiguous {self.dtype} tensors of {self.n_dofs} rows on {self.device}")
         if u.shape != y.shape or u.data_ptr() == y.data_ptr():
             raise ValueError("prepared apply: u and y must be two tensors of one shape")
         k = int(u.shape[1]) if _is_block(u) else 1
-        multi = k > 1 and self.poly_order == 1
+        multi = k > 1 and self.poly_order == 1 and fields is None
         if k > 1 and not multi:
             u_col, y_col = (torch.empty(self.n_dofs, dtype=self.dtype, device=self.device) for _ in range(2))
-            one = self._prepared_apply(alpha, beta, u_col, y_col, programs)
+            one = self._prepared_apply(alpha, beta, u_col, y_col, programs, fields)
 
             def columns():
                 for j in range(k):
@@ -1308,12 +1446,12 @@ class AssemblyEngine:
                     y[:, j].copy_(y_col)
 
             return columns
-        return self._apply_launch(alpha, beta, u, y, programs, k)
+        return self._apply_launch(alpha, beta, u, y, programs, k, fields)
 
-    def _apply_launch(self, alpha, beta, u, y, programs=None, k=1):
+    def _apply_launch(self, alpha, beta, u, y, programs=None, k=1, fields=None):
         """THE call of the matrix-free apply launches (tfem_p1_apply_rings, _multi for k >= 2,
-        _coef with `programs` = (kappa, c), _coef_multi with both, tfem_p2_apply_rows on P2) with its
-        arguments converted:
+        _coef with `programs` = (kappa, c), _coef_multi with both, _field with `fields` = (kappa, c)
+        values, tfem_p2_apply_rows on P2) with its arguments converted:
         y = K u in the engine's numbering, u None: the diagonal; u and y as the callers have
         checked them.  The returned callable enqueues on the stream that is current now."""
         d = self._inputs()
@@ -1335,7 +1473,12 @@ class AssemblyEngine:
                 raise NotImplementedError("the matrix-free operator needs the ring plan (P1, fans with a ring form)")
             where = (_native.ptr(plan["blob"]), c_void_p(plan["layout"].ctypes.data))
             head = (*head, self.n_dofs, self.quad_order, *scale)
-            if programs is not None:
+            if fields is not None:
+                if k > 1:
+                    raise NotImplementedError("the coefficient-data launch applies one vector")
+                fn = self.lib.tfem_p1_apply_rings_field
+                args = (*head, *self._field_args(fields), *where, *tail, stream)
+            elif programs is not None:
                 coef = (*head, self._program_ref(programs[0]), self._program_ref(programs[1]), *where, *tail)
                 if k > 1:
                     fn = self.lib.tfem_p1_apply_rings_coef_multi
@@ -1349,7 +1492,7 @@ class AssemblyEngine:
             else:
                 fn = self.lib.tfem_p1_apply_rings
                 args = (*head, *where, *tail, stream)
-        keep = (d, plan, u, y, programs)  # what the raw pointers above point into
+        keep = (d, plan, u, y, programs, fields)  # what the raw pointers above point into
         check = _native.check
 
         def launch():

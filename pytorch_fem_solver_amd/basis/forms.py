@@ -10,6 +10,9 @@ The user's callable is called ONCE with a proxy basis whose ``v``, ``v_grad`` an
     kappa * stiffness + c * mass  (kappa, c expressions of the coordinate columns as below: the
                                   variable coefficients of -div(kappa grad u) + c u; P1 launches
                                   evaluate them per triangle, csrc/tfem_rings_coef.hip)
+    field * stiffness + field * mass
+                                  (field = ``basis.coefficient(values)``: coefficient DATA at the
+                                  integration points or per element, csrc/tfem_rings_field.hip)
     f * v   /   v * f             f a tensor broadcastable to (..., Q, 1, 1), or an
                                   expression of the coordinate columns of
                                   ``integration_points`` (``torch.split(points, 1, dim=-1)``,
@@ -183,8 +186,9 @@ def _scaled_node(node, factor):
 class BilinearExpr(_Symbol):
     """alpha * kappa(x, y) * (v_grad @ v_grad.mT) + beta * c(x, y) * (v @ v.mT)
 
-    ``alpha`` / ``beta``: python scalars; ``kappa`` / ``c``: None (the constant 1) or a SourceExpr
-    of the coordinate columns -- the variable coefficients of -div(kappa grad u) + c u."""
+    ``alpha`` / ``beta``: python scalars; ``kappa`` / ``c``: None (the constant 1), a SourceExpr
+    of the coordinate columns or a CoefficientField (values at the integration points or per
+    element) -- the variable coefficients of -div(kappa grad u) + c u."""
 
     def __init__(self, basis, alpha, beta, kappa=None, c=None):
         super().__init__(basis)
@@ -196,6 +200,11 @@ class BilinearExpr(_Symbol):
     @property
     def has_coefficients(self):
         return self.kappa is not None or self.c is not None
+
+    @property
+    def has_data(self):
+        """A term carries coefficient DATA (a CoefficientField) rather than a program."""
+        return isinstance(self.kappa, CoefficientField) or isinstance(self.c, CoefficientField)
 
     def materialize(self):
         # the caller's operations on the real tensors: coefficient * form, scalar factor outside
@@ -226,25 +235,33 @@ class BilinearExpr(_Symbol):
             return f1, s1
         if f1 == 0.0:
             return f2, s2
+        if isinstance(s1, CoefficientField) or isinstance(s2, CoefficientField):
+            return None  # data does not add symbolically: the sum is left to torch
         n1 = _scaled_node(s1.node, f1) if s1 is not None else ("c", f1)
         n2 = _scaled_node(s2.node, f2) if s2 is not None else ("c", f2)
         return 1.0, SourceExpr(basis, ("add", n1, n2))
 
     def _sum(self, other, sign):
-        alpha, kappa = self._term(self._basis, self.alpha, self.kappa, sign * other.alpha, other.kappa)
-        beta, c = self._term(self._basis, self.beta, self.c, sign * other.beta, other.c)
-        return BilinearExpr(self._basis, alpha, beta, kappa, c)
+        stiffness = self._term(self._basis, self.alpha, self.kappa, sign * other.alpha, other.kappa)
+        mass = self._term(self._basis, self.beta, self.c, sign * other.beta, other.c)
+        if stiffness is None or mass is None:
+            return None
+        return BilinearExpr(self._basis, stiffness[0], mass[0], stiffness[1], mass[1])
 
     def __add__(self, other):
         if isinstance(other, BilinearExpr):
-            return self._sum(other, 1.0)
+            out = self._sum(other, 1.0)
+            if out is not None:
+                return out
         return super().__add__(other)
 
     __radd__ = __add__
 
     def __sub__(self, other):
         if isinstance(other, BilinearExpr):
-            return self._sum(other, -1.0)
+            out = self._sum(other, -1.0)
+            if out is not None:
+                return out
         return super().__sub__(other)
 
     # ---- products with a scalar or with a scalar field of the coordinates --------------------
@@ -252,6 +269,8 @@ class BilinearExpr(_Symbol):
         """field * self for a PURE term (stiffness only or mass only), else None."""
         if field.node[0] == "c":  # a constant written as a field: a scalar factor
             return BilinearExpr(self._basis, self.alpha * field.node[1], self.beta * field.node[1], self.kappa, self.c)
+        if self.has_data:  # program x data on one term: left to torch
+            return None
         if self.alpha != 0.0 and self.beta == 0.0 and self.c is None:
             kappa = field if self.kappa is None else SourceExpr(self._basis, ("mul", self.kappa.node, field.node))
             return BilinearExpr(self._basis, self.alpha, 0.0, kappa, None)
@@ -260,11 +279,24 @@ class BilinearExpr(_Symbol):
             return BilinearExpr(self._basis, 0.0, self.beta, None, c)
         return None
 
+    def _times_data(self, field):
+        """field * self for a PURE term that has no coefficient yet (stiffness only or mass only),
+        else None: two fields on one term, or data on a sum, are left to torch."""
+        if self.alpha != 0.0 and self.beta == 0.0 and self.kappa is None and self.c is None:
+            return BilinearExpr(self._basis, self.alpha, 0.0, field, None)
+        if self.beta != 0.0 and self.alpha == 0.0 and self.kappa is None and self.c is None:
+            return BilinearExpr(self._basis, 0.0, self.beta, None, field)
+        return None
+
     def __mul__(self, other):
         if _is_scalar(other):
             return BilinearExpr(self._basis, self.alpha * _scalar(other), self.beta * _scalar(other), self.kappa, self.c)
         if isinstance(other, SourceExpr):
             out = self._times_field(other)
+            if out is not None:
+                return out
+        if isinstance(other, CoefficientField):
+            out = self._times_data(other)
             if out is not None:
                 return out
         return super().__mul__(other)
@@ -280,6 +312,55 @@ class BilinearExpr(_Symbol):
 
     def __neg__(self):
         return BilinearExpr(self._basis, -self.alpha, -self.beta, self.kappa, self.c)
+
+
+class CoefficientField(_Symbol):
+    """``basis.coefficient(values)``: a tensor marked as a coefficient field -- values at the
+    integration points, ``(E, Q, 1, 1)`` or ``(E, Q)`` in the basis's element order and the q order of
+    the quadrature rule, or one value per element, ``(E, 1, 1, 1)``, ``(E, 1)`` or ``(E,)``, in the
+    basis's dtype.  In front of ``v_grad @ v_grad.mT`` or ``v @ v.mT`` it makes the form one that the
+    coefficient-data launches assemble and apply (csrc/tfem_rings_field.hip); everywhere else it is
+    the tensor ``(E, Q | 1, 1, 1)`` it stands for."""
+
+    def __init__(self, basis, values):
+        super().__init__(basis)
+        if isinstance(values, CoefficientField):
+            values = values.tensor
+        if not isinstance(values, torch.Tensor):
+            raise ValueError(f"coefficient: a tensor of values is expected, got {type(values).__name__}")
+        engine = getattr(basis, "_engine", None)
+        if engine is not None:
+            lead, n_quad, dtype = tuple(engine.lead_shape), int(engine.n_quad), engine.dtype
+        else:
+            points = basis.integration_points
+            lead, n_quad, dtype = tuple(points.shape[:-3]), int(points.shape[-3]), points.dtype
+        shape = tuple(values.shape)
+        ok = len(lead) == 1 and (shape in ((lead[0], n_quad, 1, 1), (lead[0], n_quad), (lead[0], 1, 1, 1),
+                                           (lead[0], 1), (lead[0],)))
+        if not ok:
+            raise ValueError(f"coefficient: values of shape {shape}; expected ({lead[0] if lead else 'E'}, {n_quad}) "
+                             f"values at the integration points or ({lead[0] if lead else 'E'},) values per element "
+                             "(with trailing dimensions of 1)")
+        if values.dtype != dtype:
+            raise ValueError(f"coefficient: values of dtype {values.dtype}, the basis works in {dtype}")
+        object.__setattr__(self, "tensor", values.reshape(lead[0], -1, 1, 1))
+
+    def materialize(self):
+        return self.tensor
+
+    @property
+    def per_element(self):
+        return self.tensor.shape[1] == 1
+
+    def __mul__(self, other):
+        if isinstance(other, BilinearExpr):
+            return other.__mul__(self)
+        return super().__mul__(other)
+
+    def __rmul__(self, other):
+        if isinstance(other, BilinearExpr):
+            return other.__mul__(self)
+        return super().__rmul__(other)
 
 
 class LinearExpr(_Symbol):
@@ -729,6 +810,6 @@ def trace(function, basis, args, kwargs):
 
 
 __all__ = [
-    "BilinearExpr", "LinearExpr", "SourceExpr", "PointsSymbol", "TracingBasis", "Untraceable",
+    "BilinearExpr", "CoefficientField", "LinearExpr", "SourceExpr", "PointsSymbol", "TracingBasis", "Untraceable",
     "compile_ops", "compile_program", "materialize", "trace", "OPS", "math",
 ]

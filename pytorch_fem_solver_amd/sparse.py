@@ -465,6 +465,37 @@ class _OperatorApply(torch.autograd.Function):
         return ctx.op._apply(grad_out), None
 
 
+class _FieldApply(torch.autograd.Function):
+    """u -> K u of an operator with coefficient DATA, differentiable in u (the same application:
+    K^T = K) and in the values kappa, c at the integration points: one tfem_p1_field_adjoint call
+    gives d (g^T K u) / d kappa[e][q] and d / d c[e][q].  `kappa` / `c` are the (E, Q) views of the
+    marked tensors (an expanded view for one value per element: autograd sums over q through it) or
+    None; the forward launch reads the operator's own compact copies, not these."""
+
+    @staticmethod
+    def forward(ctx, u, kappa, c, op):
+        ctx.op = op
+        ctx.save_for_backward(u.detach())
+        return op._apply(u.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        op = ctx.op
+        (u,) = ctx.saved_tensors
+        need_u, need_kappa, need_c = ctx.needs_input_grad[:3]
+        grad_u = op._apply(grad_out) if need_u else None
+        grad_kappa = grad_c = None
+        if need_kappa or need_c:
+            grad_kappa, grad_c = op._engine.field_adjoint(op.alpha, op.beta, grad_out, u, need_kappa, need_c)
+            sources = op._field_sources
+            if grad_kappa is not None:
+                grad_kappa = grad_kappa.to(sources[0].device)
+            if grad_c is not None:
+                grad_c = grad_c.to(sources[1].device)
+        return grad_u, grad_kappa, grad_c, None
+
+
 class FormOperator:
     """The global operator of a bilinear form, to apply and to solve with, without necessarily
     storing it (``Basis.integrate_bilinear_form(..., layout="operator")`` or ``layout="matrix_free"``).
@@ -473,7 +504,10 @@ class FormOperator:
     engine has a ring plan; every ``matvec`` is one tfem_p1_apply_rings launch that forms the rows
     of K in registers and writes K u -- the values of K are never stored.  The operator may carry
     the source programs of variable coefficients kappa(x, y), c(x, y) (tfem_p1_apply_rings_coef then:
-    the programs are evaluated per triangle inside the launch).  Otherwise the operator
+    the programs are evaluated per triangle inside the launch), or coefficient DATA -- values of kappa
+    and c at the integration points or per element (``basis.coefficient``; tfem_p1_apply_rings_field:
+    the values of a tile's elements are read once per tile and reduced in LDS); ``matvec`` is then also
+    differentiable in the values (tfem_p1_field_adjoint), blocks go column by column.  Otherwise the operator
     wraps the CSRMatrix of today's assembly and applies it with tfem_csr_spmv (P2, fractures, any
     other integrand, meshes without a ring plan); the interface and the results are the same.
     Vectors are taken and returned in the caller's DoF numbering, of shape (N,) or (N, 1); a block
@@ -490,7 +524,7 @@ class FormOperator:
     column indices but no values; a block goes column by column."""
 
     def __init__(self, n, dtype, device, assemble, engine=None, alpha=0.0, beta=0.0, symmetric=True,
-                 programs=None, p2_rows=False, matrix_free=None):
+                 programs=None, p2_rows=False, matrix_free=None, fields=None, field_sources=None):
         self.shape = (int(n), int(n))
         self.dtype = dtype
         self.device = device
@@ -499,6 +533,10 @@ class FormOperator:
         self.alpha, self.beta = float(alpha), float(beta)
         #: (kappa, c) source programs of a variable-coefficient form (None: constant coefficients)
         self._programs = programs
+        #: (kappa, c) coefficient DATA, (E, Q | 1) on the engine's device (None: no data), and the
+        #: tensors the caller marked (the autograd leaves or their descendants)
+        self._fields = fields
+        self._field_sources = field_sources if field_sources is not None else (None, None)
         self._symmetric = symmetric
         self._csr = None
         #: P2 over the row plan (tfem_p2_apply_rows) instead of P1 over the ring plan
@@ -515,7 +553,9 @@ class FormOperator:
         """Decided on first use: the ring plan is built then (as for an assembly), not before."""
         if self._matrix_free is None:
             try:
-                if self._programs is not None:
+                if self._fields is not None:
+                    self._matrix_free = self._engine.field_refusal(self.beta, "apply") is None
+                elif self._programs is not None:
                     self._matrix_free = self._engine.supports_coefficients()
                 else:
                     self._matrix_free = self._engine.ring_plan() is not None
@@ -525,6 +565,8 @@ class FormOperator:
 
     def _rows(self, u):
         """K u (u None: diag K) by one launch in the engine's numbering."""
+        if self._fields is not None:
+            return self._engine._apply_rings_field(self.alpha, self.beta, self._fields, u)
         if self._programs is not None:
             return self._engine._apply_rings_coef(self.alpha, self.beta, *self._programs, u)
         if self._p2_rows:
@@ -551,7 +593,9 @@ class FormOperator:
         flat = self._check(x)
         if self.matrix_free:
             engine = self._engine
-            if self._programs is not None:
+            if self._fields is not None:
+                y = engine._home(engine.apply_field(self.alpha, self.beta, self._fields, flat))
+            elif self._programs is not None:
                 y = engine._home(engine.apply_coef(self.alpha, self.beta, *self._programs, flat))
             else:
                 y = engine._home(engine.apply(self.alpha, self.beta, flat))
@@ -560,7 +604,13 @@ class FormOperator:
         return y.reshape(x.shape)
 
     def matvec(self, x):
-        """K x for x of shape (N,), (N, 1) or (N, k); differentiable in x for symmetric forms."""
+        """K x for x of shape (N,), (N, 1) or (N, k); differentiable in x for symmetric forms, and in
+        the values of coefficient data that require grad."""
+        if torch.is_grad_enabled() and self.matrix_free and any(
+                s is not None and s.requires_grad for s in self._field_sources):
+            n_elems, n_quad = self._engine.n_elems, self._engine.n_quad
+            views = [None if s is None else s.reshape(n_elems, -1).expand(n_elems, n_quad) for s in self._field_sources]
+            return _FieldApply.apply(x, *views, self)
         if x.requires_grad and torch.is_grad_enabled():
             if not self._symmetric:
                 raise NotImplementedError("matvec: the gradient needs the transpose of a non-symmetric form")
@@ -574,6 +624,8 @@ class FormOperator:
         """diag(K), shape (N,)."""
         if self.matrix_free:
             engine = self._engine
+            if self._fields is not None:
+                return engine._home(engine.operator_diagonal_field(self.alpha, self.beta, self._fields))
             if self._programs is not None:
                 return engine._home(engine.operator_diagonal_coef(self.alpha, self.beta, *self._programs))
             return engine._home(engine.operator_diagonal(self.alpha, self.beta))
@@ -582,8 +634,8 @@ class FormOperator:
     def _rows_into(self):
         """``matvec_into`` of ``fused_conjugate_gradients``: the launch of ``_rows`` into a given
         buffer, in the engine's numbering."""
-        programs = self._programs
-        return _into(lambda u, out: self._engine._prepared_apply(self.alpha, self.beta, u, out, programs))
+        programs, fields = self._programs, self._fields
+        return _into(lambda u, out: self._engine._prepared_apply(self.alpha, self.beta, u, out, programs, fields))
 
     def solve_cg(self, b, free=None, x0=None, rtol=1e-12, maxiter=None, loop=None):
         """Jacobi-preconditioned CG on the DoFs ``free``: the contract and the results of
@@ -656,4 +708,6 @@ class FormOperator:
             kind = "matrix-free, variable coefficients" if self._matrix_free else "unresolved, variable coefficients"
         if self._p2_rows and self._matrix_free:
             kind = "matrix-free, P2 rows"
+        if self._fields is not None and self._matrix_free is not False:
+            kind = "matrix-free, coefficient data" if self._matrix_free else "unresolved, coefficient data"
         return f"FormOperator(shape={self.shape}, dtype={self.dtype}, device={self.device}, {kind})"

@@ -4,6 +4,7 @@ package for the assembly path, reference torch_fem/__init__.py:3-28)."""
 
 from pytorch_fem_solver_amd import (  # noqa: F401
     Basis,
+    CoefficientField,
     CSRMatrix,
     ElementLine,
     ElementTri,
@@ -24,4 +25,5 @@ __all__ = [
     "ElementTri",
     "FracturesTri",
     "MeshTri",
+    "CoefficientField",
 ]
