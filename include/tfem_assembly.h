@@ -183,6 +183,25 @@ int tfem_csr_gather(const void *local, int real_bytes, const int64_t *gptr, cons
 int tfem_csr_spmv(const int64_t *rowptr, const int32_t *colind, const void *vals, int real_bytes,
                   int64_t n_rows, const void *x, void *y, void *stream);
 
+/* Y = A X of the same operator for n_vec vectors at once (DEVICE): x is n_cols x n_vec and y
+ * n_rows x n_vec reals, ROW-major (the n_vec values of a DoF consecutive: the layout of the
+ * tfem_cg_* launches and of tfem_p1_apply_rings_multi), y[i][c] = sum_p vals[p] * x[colind[p]][c].
+ * Replaces, like tfem_csr_spmv, the consumer of the assembled operator on the reference side
+ * (abstract_basis.py:177-195) where that operator meets several right-hand sides: one launch for
+ * any n_vec >= 1 instead of n_vec launches that each read the matrix.  Eight lanes per row, lane
+ * `sub` takes the entries start + sub + 8 t in order, butterfly over 4, 2, 1 -- the arithmetic of
+ * tfem_csr_spmv, so column c of y is bit for bit what tfem_csr_spmv gives for the contiguous copy
+ * of column c of x, whatever n_vec is.  n_vec in {2, 4, 8} with x and y both aligned to
+ * min(16, n_vec * real_bytes) bytes: rows move in accesses of that width; any other width or
+ * alignment: passes over 8 columns with scalar accesses, inside the one launch.  Every entry of y
+ * is written once (0 for an empty row), nothing else.  No allocation, no synchronisation.
+ * Refused before anything is launched (TFEM_ERR_INVALID_ARGUMENT): real_bytes not 4 or 8, a
+ * negative n_rows, n_cols or n_vec, NULL rowptr, x (with n_cols > 0) or y, overlapping extents of
+ * x and y; TFEM_ERR_INDEX_RANGE: n_rows >= 2^36 or an extent beyond 2^62 bytes.  n_rows == 0 or
+ * n_vec == 0 succeeds and launches nothing.  colind is trusted to lie in [0, n_cols). */
+int tfem_csr_spmm(const int64_t *rowptr, const int32_t *colind, const void *vals, int real_bytes,
+                  int64_t n_rows, int64_t n_cols, int n_vec, const void *x, void *y, void *stream);
+
 /* A P1 DoF vector u (n_verts entries) on both sides of every interior edge: replaces the
  * tensor branch of Basis.interpolate(InteriorEdgesBasis, u) (reference basis.py:98-177;
  * SURVEY 8(f) f-2).  conn: (n_elems, 3) int32 cell vertices; edge_cells: (n_edges, 2) int64

@@ -126,12 +126,24 @@ class CSRMatrix:
         return dense
 
     def matvec(self, x):
-        """A @ x for x of shape (N,) or (N, 1): libtfem_hip's CSR kernel on the GPU.  (N, k) with
-        k >= 2: the same launch once per column, result (N, k)."""
+        """A @ x for x of shape (N,) or (N, 1): libtfem_hip's CSR kernel on the GPU (tfem_csr_spmv).
+        (N, k) with k >= 2 gives (N, k): on the GPU ONE tfem_csr_spmm launch on the contiguous
+        row-major block (the matrix is read once for the k columns; with ``perm`` one row gather
+        on the way in and one on the way out), column j bit for bit what the single launch gives
+        for column j; on the host column by column."""
         if _is_block(x):
             if x.shape[0] != self.shape[1]:
                 raise ValueError(f"matvec: x has {x.shape[0]} rows, the operator {self.shape[1]} columns")
-            return torch.stack([self.matvec(x[:, j]) for j in range(x.shape[1])], dim=1)
+            if not self.values.is_cuda:
+                return torch.stack([self.matvec(x[:, j]) for j in range(x.shape[1])], dim=1)
+            block = x.to(self.device, self.dtype)
+            if self.perm is not None:
+                return self._stored().matvec(block[self.perm])[self._inverse()]
+            block = block.contiguous()
+            y = torch.empty(self.shape[0], block.shape[1], dtype=self.dtype, device=self.device)
+            with torch.cuda.device(self.device):
+                self._prepared_spmv(block, y)()
+            return y
         if self.perm is not None:
             flat = x.to(self.device, self.dtype).reshape(-1)
             return self._stored().matvec(flat[self.perm])[self._inverse()].reshape(x.shape)
@@ -148,28 +160,25 @@ class CSRMatrix:
 
     def _prepared_spmv(self, x, y):
         """y = A x in the STORED numbering into a given y, nothing allocated: x and y contiguous
-        device tensors of the operator's dtype, (N,) or (N, k) (a block: the launch once per column
-        through a contiguous pair of columns).  The arguments are converted once; the returned
-        callable only enqueues, on the stream that is current now."""
+        device tensors of the operator's dtype, (N,) or (N, k) of the same shape (a block: ONE
+        tfem_csr_spmm launch straight on the two row-major buffers, no staging vector and no copy;
+        (N,) and (N, 1): tfem_csr_spmv).  The arguments are converted once; the returned callable
+        only enqueues, on the stream that is current now."""
         n = self.shape[0]
         for t, rows in ((x, self.shape[1]), (y, n)):
             if t.dtype != self.dtype or t.device != self.device or not t.is_contiguous() or t.shape[0] != rows:
                 raise ValueError(f"spmv: contiguous {self.dtype} tensors of {rows} rows on {self.device}")
+        matrix = (_native.ptr(self.crow_indices), _native.ptr(self.col_indices), _native.ptr(self.values),
+                  self.values.element_size(), n)
+        vectors = (_native.ptr(x), _native.ptr(y), _native.current_stream(self.device))
         if _is_block(x):
-            k = x.shape[1]
-            x_col, y_col = (torch.empty(rows, dtype=self.dtype, device=self.device) for rows in (self.shape[1], n))
-            one = self._prepared_spmv(x_col, y_col)
-
-            def columns():
-                for j in range(k):
-                    x_col.copy_(x[:, j])
-                    one()
-                    y[:, j].copy_(y_col)
-
-            return columns
-        fn = _native.load().tfem_csr_spmv
-        args = (_native.ptr(self.crow_indices), _native.ptr(self.col_indices), _native.ptr(self.values),
-                self.values.element_size(), n, _native.ptr(x), _native.ptr(y), _native.current_stream(self.device))
+            if y.shape[1:] != x.shape[1:]:
+                raise ValueError(f"spmv: x has {x.shape[1]} columns, y has shape {tuple(y.shape)}")
+            fn = _native.load().tfem_csr_spmm
+            args = (*matrix, self.shape[1], x.shape[1], *vectors)
+        else:
+            fn = _native.load().tfem_csr_spmv
+            args = (*matrix, *vectors)
         keep = (self, x, y)  # what the raw pointers above point into
 
         def launch():
@@ -513,8 +522,11 @@ class FormOperator:
     Vectors are taken and returned in the caller's DoF numbering, of shape (N,) or (N, 1); a block
     (N, k) of k >= 2 vectors gives (N, k): matrix-free on P1 by ONE call that forms the rows of K
     once for the k columns (tfem_p1_apply_rings_multi; with coefficient programs
-    tfem_p1_apply_rings_coef_multi, which evaluates the programs once for the k columns), every
-    other operator by its single-vector launch once per column.
+    tfem_p1_apply_rings_coef_multi, which evaluates the programs once for the k columns), the
+    operator that wraps the CSR by ONE tfem_csr_spmm launch that reads the matrix once for the k
+    columns (``CSRMatrix.matvec``; also the backward of ``matvec`` in the block, and every iteration
+    of the block CG loops), the P2 matrix-free operator and the operator with coefficient data by
+    their single-vector launch once per column.
 
     ``layout="matrix_free"`` is the strict request: the plan is built at the call, the operator it
     returns is matrix-free from the start (``matrix_free`` True), and a basis or form without the
