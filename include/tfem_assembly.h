@@ -454,6 +454,38 @@ int tfem_p1_assemble_rings_source(const void *coords, int real_bytes, int64_t n_
                                   void *vals, int64_t nnz, const tfem_source_program *source,
                                   int64_t n_elems, void *fout, void *stream);
 
+/* The caller vouches for ONE coordinate array (DEVICE pointer `coords`, as it is passed to the
+ * launches): every |x|, |y| in it is <= max_abs_coord (finite, >= 0).  Array and bound are kept in
+ * plan_layout_host[29] and [31] (HOST, the 32 values of tfem_ring_plan_sizes; [29] = 0: no bound)
+ * and travel with the layout to the launches.  An fp64 tfem_p1_assemble_rings_source / _range launch
+ * that is given THAT array proves ONCE, on the host, that a SIN / COS applied to a coordinate push
+ * stays on the fast path (tfem_source_trig_proof) and skips the range test of every value; a launch
+ * with another coordinate array, without a bound, or where the proof fails tests every value as
+ * before.  The integration points are convex combinations of the vertices, so the bound holds for
+ * them.  A NULL array or a negative or non-finite max_abs_coord withdraws the bound.  The bound is
+ * a statement about the array's CONTENTS: a caller that writes other coordinates into the same
+ * array must withdraw or renew it.  (The bound is state of the layout and not an argument of a
+ * launch so that the launches keep their entry points and signatures.) */
+int tfem_ring_plan_vouch_coords(int64_t *plan_layout_host, const void *coords, double max_abs_coord);
+
+/* ops_out[i] (HOST, TFEM_SOURCE_MAX_OPS entries, 0 behind the program) = the operation codes a
+ * tfem_p1_assemble_rings_source / _range launch with these arguments hands to its kernel: the
+ * program's own, with TFEM_SRC_OP_COUNT (sine) / TFEM_SRC_OP_COUNT + 1 (cosine) in place of the
+ * SIN / COS whose range the launch has proven from the vouched bound.  For tests and tools: what a
+ * launch decided is otherwise visible in its time only. */
+int tfem_p1_rings_source_ops(const void *coords, int real_bytes, int quad_order,
+                             const int64_t *plan_layout_host, const tfem_source_program *source,
+                             uint8_t *ops_out);
+
+/* fast_out[i] (HOST, TFEM_SOURCE_MAX_OPS entries) = 1 where operation i of `program` is a SIN or
+ * COS whose operand is the PUSH_X / PUSH_Y directly in front of it, with constant c, and
+ *   |c| * max_abs_coord * (1 + 1e-9) < 1e9 / 2
+ * (1e9: below it the fp64 kernels take their own sin / cos, above it the library's), 0 elsewhere.
+ * Returns the number of such operations; 0 for an invalid program or a max_abs_coord that is
+ * negative or not finite. */
+int tfem_source_trig_proof(const tfem_source_program *program, double max_abs_coord,
+                           uint8_t *fast_out);
+
 /* Variable coefficients: the CSR values of
  *   alpha * int kappa(x, y) grad u . grad v + beta * int c(x, y) u v
  * over a ring plan, kappa and c source programs (HOST) evaluated at the integration points inside

@@ -9,6 +9,7 @@ this package: without the library or without a GPU every method raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from ctypes import c_void_p
 
@@ -1034,6 +1035,39 @@ class AssemblyEngine:
                              f"entries on {self.device}")
         return given.view(-1)
 
+    def _vouch_ring_coords(self, rings, coords):
+        """The bound max |x|, |y| of the coordinate array the ring launches are given, measured once
+        per mesh and handed to the library with the plan's layout (tfem_ring_plan_vouch_coords, for
+        THIS array's address): an fp64 launch of a source program then proves its sin / cos of a
+        coordinate in range once instead of testing every value.  The engine vouches for the array as
+        long as torch has not written to it since the measurement (its version counter); after a
+        write the bound is withdrawn for good and the launches test every value again.
+        The limit of that guard: the array can be the caller's own tensor (coordinates that already
+        live on the device are not copied), and a write that torch does not see -- through `.data`,
+        a raw pointer, another library's kernel, a DLPack alias -- does not move the counter.  Such
+        a write that also takes a sin / cos argument to 1e9 or beyond gives that value the accuracy
+        of the fast reduction instead of the library function's; nothing faults.
+        The measurement reads a value back (one device synchronisation per mesh), so it is put off
+        while a stream capture is under way: launches captured before any eager one test every value."""
+        state = rings.get("coords_version")
+        version = coords._version
+        if state == version:
+            return
+        layout = c_void_p(rings["layout"].ctypes.data)
+        if state is None:
+            if torch.cuda.is_current_stream_capturing():
+                return
+            bound = 0.0
+            if coords.numel():  # (NaN coordinates give a NaN here: no bound)
+                lo, hi = torch.aminmax(coords)
+                bound = max(abs(float(lo)), abs(float(hi)))
+            _native.check(self.lib.tfem_ring_plan_vouch_coords(layout, _native.ptr(coords),
+                                                               bound if math.isfinite(bound) else -1.0))
+            rings["coords_version"] = version
+        elif state != "withdrawn":
+            _native.check(self.lib.tfem_ring_plan_vouch_coords(layout, None, -1.0))
+            rings["coords_version"] = "withdrawn"
+
     def _assemble_rings(self, alpha, beta, fq=None, want_matrix=True, out=(None, None), source=None,
                         tiles=None):
         """One tfem_p1_assemble_rings launch: CSR values of alpha*stiffness + beta*mass and,
@@ -1051,6 +1085,8 @@ class AssemblyEngine:
             fq = fq.to(self.device, self.dtype).reshape(self.n_elems, self.n_quad).contiguous()
         if with_load:
             fout = self._output(out[1], self.n_dofs, "load vector")
+        if source is not None:
+            self._vouch_ring_coords(rings, d["coords"])
         with torch.cuda.device(self.device):
             if tiles is not None:
                 _native.check(
@@ -1531,9 +1567,14 @@ class AssemblyEngine:
         keep = (d, rings, vals, fout, fq, program)  # what the raw pointers above point into
         launch_fn, device, check = self.lib.tfem_p1_assemble_rings_range, self.device, _native.check
         current_stream = torch.cuda.current_stream
+        coords, vouch = d["coords"], self._vouch_ring_coords
+        if program is not None:
+            vouch(rings, coords)
 
         def launch(stream=None):
             """Enqueue on `stream` (a torch.cuda.Stream; default: the current one)."""
+            if program is not None and coords._version != rings.get("coords_version"):
+                vouch(rings, coords)  # written since the bound was measured: withdrawn
             handle = (stream if stream is not None else current_stream(device)).cuda_stream
             status = launch_fn(*fixed, c_void_p(handle))
             if status:

@@ -96,6 +96,39 @@ static void *pick_ring_kernel(int slots, bool mass, bool chunk, int nq, bool src
   return chunk ? pick_ring_mass<T, 15, true>(kmat, mass, nq) : pick_ring_mass<T, 15, false>(kmat, mass, nq);
 }
 
+// programs that never hold more than two values: three elements per pass of the interpreter
+static bool ring_src_wide(const tfem_source_program *source) {
+  bool wide = src_depth(source) <= 2;
+  if (const char *v = std::getenv("TFEM_SRC_WIDE")) wide = wide && std::atoi(v) != 0;  // developer switch
+  return wide;
+}
+
+// The program as the launch hands it to the kernel.  With the caller's bound on THIS coordinate array
+// (tfem_ring_plan_vouch_coords: layout[29] the array it vouched for, layout[31] the bound) the fp64
+// launches of the wide interpreter -- the one that knows the proven operations -- skip the range tests
+// of the SIN / COS the host proves; everything else is converted as it is.
+template <typename T>
+static int ring_src_convert(const int64_t *z, const void *coords, int nq, const tfem_source_program *source,
+                            SrcProgram<T> *out) {
+  double coord_bound = -1.0;
+  if (z[29] != 0 && uintptr_t(z[29]) == reinterpret_cast<uintptr_t>(coords))
+    std::memcpy(&coord_bound, &z[31], sizeof(coord_bound));
+  if (sizeof(T) == 8 && coord_bound >= 0.0 && ring_src_runs_wide(nq, ring_src_wide(source)))
+    return src_convert_proven<T>(source, coord_bound, out);
+  return src_convert<T>(source, out);
+}
+
+template <typename T>
+static int ring_src_ops(const int64_t *z, const void *coords, int nq, const tfem_source_program *source,
+                        uint8_t *ops_out) {
+  SrcProgram<T> device;
+  const int st = ring_src_convert<T>(z, coords, nq, source, &device);
+  if (st != TFEM_OK) return st;
+  std::memset(ops_out, 0, kSrcMaxOps);
+  for (int i = 0; i < device.n_ops; ++i) ops_out[i] = uint8_t((device.opw[i >> 2] >> (8 * (i & 3))) & 0xFFu);
+  return TFEM_OK;
+}
+
 template <typename T>
 static int launch_rings(const RingLaunch &L) {
   TriTables tables;
@@ -176,7 +209,7 @@ static int launch_rings(const RingLaunch &L) {
     a.chain_len = int(z[25]);
     if (a.chain_len < 1 || z[24] == 0 || z[26] == 0)
       return fail(TFEM_ERR_INVALID_ARGUMENT, "the ring plan carries no chain order (layout of an older build?)");
-    st = src_convert<T>(L.source, &a.src);
+    st = ring_src_convert<T>(z, L.coords, tables.nq, L.source, &a.src);
     if (st != TFEM_OK) return st;
   }
   const int64_t t_first = L.tile_first, t_count = L.tile_count < 0 ? z[0] - L.tile_first : L.tile_count;
@@ -222,8 +255,7 @@ static int launch_rings(const RingLaunch &L) {
   a.plain_stores = !load;
   if (const char *v = std::getenv("TFEM_RINGS_STORES")) a.plain_stores = std::strcmp(v, "plain") == 0;
   // programs that never hold more than two values: three elements per pass of the interpreter
-  bool wide = src && src_depth(L.source) <= 2;
-  if (const char *v = std::getenv("TFEM_SRC_WIDE")) wide = wide && std::atoi(v) != 0;  // developer switch
+  const bool wide = src && ring_src_wide(L.source);
   void *kernel = pick_ring_kernel<T>(slots, mass, chunk, load ? tables.nq : 0, src, kmat, wide);
   if (!kernel) return fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
   // resident workgroups: what LDS and registers allow per CU, on every CU
@@ -286,6 +318,18 @@ static int ring_entry(const void *coords, int real_bytes, int64_t n_verts, int q
 }  // namespace tfem
 
 extern "C" {
+
+int tfem_p1_rings_source_ops(const void *coords, int real_bytes, int quad_order, const int64_t *plan_layout_host,
+                             const tfem_source_program *source, uint8_t *ops_out) {
+  using namespace tfem;
+  if (real_bytes != 4 && real_bytes != 8) return fail(TFEM_ERR_INVALID_ARGUMENT, "real_bytes must be 4 or 8");
+  if (!plan_layout_host || !source || !ops_out) return fail(TFEM_ERR_INVALID_ARGUMENT, "NULL pointer");
+  TriTables tables;
+  if (!build_tri_tables(quad_order, real_bytes, &tables))
+    return fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
+  return real_bytes == 8 ? ring_src_ops<double>(plan_layout_host, coords, tables.nq, source, ops_out)
+                         : ring_src_ops<float>(plan_layout_host, coords, tables.nq, source, ops_out);
+}
 
 int tfem_ring_capacity(int what) {
   using namespace tfem;

@@ -1206,6 +1206,19 @@ int tfem_ring_plan_pack(const void *plan_handle, void *blob_host) {
   return TFEM_OK;
 }
 
+int tfem_ring_plan_vouch_coords(int64_t *plan_layout_host, const void *coords, double max_abs_coord) {
+  if (!plan_layout_host) return tfem::fail(TFEM_ERR_INVALID_ARGUMENT, "plan_layout_host is NULL");
+  // layout[29]: the coordinate array the bound is about (0: no bound), layout[31]: the bound's bit pattern
+  int64_t bits = 0, array = 0;
+  if (coords && max_abs_coord >= 0.0 && std::isfinite(max_abs_coord)) {
+    std::memcpy(&bits, &max_abs_coord, sizeof(bits));
+    array = int64_t(reinterpret_cast<uintptr_t>(coords));
+  }
+  plan_layout_host[29] = array;
+  plan_layout_host[31] = bits;
+  return TFEM_OK;
+}
+
 void tfem_ring_plan_destroy(void *plan_handle) { delete static_cast<tfem::RingPlan *>(plan_handle); }
 
 }  // extern "C"

@@ -512,6 +512,9 @@ __device__ __forceinline__ RingDesc ring_desc(const unsigned char *plan, unsigne
 //   D  coordinates of tile k+1 -> xy[(k+1) & 1]; stage -> global stores of tile k
 //   E  LDS barrier (the only one): xy[(k+1) & 1] is complete, nobody reads xy[k & 1] any more
 // Neither a load's latency nor a store's acknowledgement is waited for inside an iteration.
+// The fp64 launches of a source program on the wide interpreter (kCoordsToLds) fetch the coordinates differently: the loads
+// of tile k+1 are issued at the top of iteration k, in front of phase G, and write xy[(k+1) & 1]
+// themselves (16 bytes per lane, buffer_load ... lds) -- no register holds them, D copies nothing.
 // ---------------------------------------------------------------------------------------
 constexpr int kRingHaloCap = kRingBlock;  // halo vertices per tile: one per lane
 constexpr int kRingElemPerLane = 3;       // elements staged per tile <= 3 * kRingBlock
@@ -572,6 +575,11 @@ template <typename T, int SLOTS, bool MASS, bool CHUNK, int QL, bool, bool KMAT 
 __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (SLOTS > 7 && QL == 0) ? 3 : 1) void k_p1_rings(const RingArgs<T> a) {
   constexpr bool LOAD = QL > 0;
   constexpr bool FQ = LOAD && !SRC;  // source values streamed from memory
+  // fp64 source programs of the wide interpreter: a lane's coordinate pair is 16 bytes, which a buffer
+  // load can write to LDS itself (float32: 8 bytes, a size the LDS form does not have -- those keep the
+  // register path; so does the general interpreter, SRC = 1, whose launches were measured 2 % SLOWER
+  // with it: 264 -> 270 us for a depth-3 program at 1e7 elements, profiles/fused_lds_direct.log)
+  constexpr bool kCoordsToLds = SRC == 2 && sizeof(T) == 8;
   static_assert(KMAT || LOAD, "nothing to assemble");
   static_assert(LOAD || !SRC, "a source program needs a load vector");
   constexpr int kEW = (12 * SLOTS + 31) / 32;  // dwords of packed 12-bit slot codes per row: 3 or 6
@@ -915,12 +923,15 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
         se_ld[FQ ? i + 2 : 0] = v.z;
       }
     }
-    ring_load_xy<T>(r_coords, g_own, own_ld[0], own_ld[1]);
-    ring_load_xy<T>(r_coords, g_halo, halo_ld[0], halo_ld[1]);
+    if constexpr (!kCoordsToLds) {
+      ring_load_xy<T>(r_coords, g_own, own_ld[0], own_ld[1]);
+      ring_load_xy<T>(r_coords, g_halo, halo_ld[0], halo_ld[1]);
+    }
     if (SRC)  // local id of the row's vertex in the previous tile of the chain block (0xFFFF: none)
       hin_ld = __builtin_amdgcn_raw_buffer_load_b16(r_plan, a.off_hin + row * 2u, 0, 0);
   };
   auto park = [&](const RingDesc &d, T *dst) {
+    if constexpr (kCoordsToLds) return;
     const int r = d.row0 + lane;
     if (r < d.row1) {
       dst[2 * r] = own_ld[0];
@@ -930,6 +941,21 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     if (h < d.n_vert) {
       dst[2 * h] = halo_ld[0];
       dst[2 * h + 1] = halo_ld[1];
+    }
+  };
+  // kCoordsToLds: the coordinates of a tile straight from memory into `dst`, 16 bytes per lane and no
+  // register in between (buffer_load_dwordx4 ... lds: lane l of the wave lands 16 l bytes behind the
+  // wave-uniform LDS base in m0).  The own rows land at dst[2 (row0 + l)], halo vertex n_own + tid at
+  // dst[2 (n_own + 64 wave + l)]: where `park` puts them.  The bounds tests stay branches -- a lane
+  // outside them is inactive and writes nothing.  The loads count in vmcnt like any other.
+  auto load_xy_lds = [&](const RingDesc &d, unsigned g_own, unsigned g_halo, T *dst) {
+    if constexpr (kCoordsToLds) {
+      typedef __attribute__((address_space(3))) void *lds_ptr;
+      if (d.row0 + lane < d.row1)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r_coords, (lds_ptr)(dst + 2 * d.row0), 16, g_own * 16u, 0, 0, 0);
+      if (d.n_own + tid < d.n_vert)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r_coords, (lds_ptr)(dst + 2 * (d.n_own + 64 * wave)), 16,
+                                                 g_halo * 16u, 0, 0, 0);
     }
   };
 
@@ -944,6 +970,7 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   load_eids(dc, eid);
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   load_tile(dc, gid_own, gid_halo);
+  load_xy_lds(dc, gid_own, gid_halo, xy);
   load_fq(dc, eid);
   load_tverts(dc, tev_ld, 0);
   if (t_n >= 0) {
@@ -994,6 +1021,10 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
       }
     };
     if (SRC) {
+      // kCoordsToLds: the coordinates of tile k+1 (its vertex ids arrived in iteration k-1) set off
+      // towards the other buffer, whose last readers ended at barrier E of iteration k-1.  They hold
+      // no register and are in flight during the whole of G; C's vmcnt(0) and barrier E publish them.
+      if (t_n >= 0) load_xy_lds(dn, gid_own, gid_halo, xy + (cur ^ 1) * 2 * a.lds_vert);
       // ---- G ---- source values of tile k (its coordinates are complete).  Before A: the
       // registers of tile k+1's loads are not live while the program runs (3 workgroups per CU)
       compute_g(dc, tev, xy + cur * 2 * a.lds_vert, accs + a_cur * acc_stride, k);
@@ -1130,6 +1161,10 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
 // wide: the three-elements-per-pass interpreter (programs of depth <= 2)
 template <typename T>
 void *pick_ring_src_kernel(int slots, bool mass, bool chunk, int nq, bool kmat, bool wide);
+// Which interpreter pick_ring_src_kernel's launch runs (`wide`: the program's depth allows the wide
+// one): with Q = 6 the wide interpreter would hold 2 x 18 doubles, so it keeps the one-element form.
+// The proven sin / cos operations (src_convert_proven) are known to the wide interpreter only.
+inline bool ring_src_runs_wide(int nq, bool wide) { return wide && nq <= 4; }
 
 // What every launch over a ring plan (layout z[], tfem_rings_host.cpp) sets alike: the capacity
 // check, the coordinate and plan extents, the section offsets, the tile count (the whole plan),

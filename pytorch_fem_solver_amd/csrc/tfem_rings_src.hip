@@ -47,8 +47,7 @@ static void *pick_src_slots(int slots, bool mass, bool chunk, int nq, bool kmat)
 
 template <typename T>
 void *pick_ring_src_kernel(int slots, bool mass, bool chunk, int nq, bool kmat, bool wide) {
-  // the wide interpreter with Q = 6 would hold 2 x 18 doubles: it keeps the one-element form
-  if (wide && nq <= 4) return pick_src_slots<T, 2>(slots, mass, chunk, nq, kmat);
+  if (ring_src_runs_wide(nq, wide)) return pick_src_slots<T, 2>(slots, mass, chunk, nq, kmat);
   return pick_src_slots<T, 1>(slots, mass, chunk, nq, kmat);
 }
 

@@ -3,6 +3,7 @@
 // (n_elems, Q) source values for the assembly entry points that take them from memory.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 
 #include "tfem_common.hpp"
@@ -70,6 +71,42 @@ int src_convert(const tfem_source_program *in, SrcProgram<T> *out) {
 }
 template int src_convert<double>(const tfem_source_program *, SrcProgram<double> *);
 template int src_convert<float>(const tfem_source_program *, SrcProgram<float> *);
+
+int src_trig_proof(const tfem_source_program *in, double coord_bound, uint8_t (&fast)[kSrcMaxOps]) {
+  std::memset(fast, 0, sizeof(fast));
+  if (!in || in->n_ops < 1 || in->n_ops > kSrcMaxOps) return 0;
+  if (!(coord_bound >= 0.0) || !std::isfinite(coord_bound)) return 0;
+  int proven = 0;
+  for (int i = 1; i < in->n_ops; ++i) {
+    const int op = in->ops[i], before = in->ops[i - 1];
+    if (op != TFEM_SRC_SIN && op != TFEM_SRC_COS) continue;
+    if (before != TFEM_SRC_PUSH_X && before != TFEM_SRC_PUSH_Y) continue;
+    // the push leaves c * (l^T X): |l^T X| <= the bound, the roundings of the four operations are
+    // far inside the margin and the factor 2
+    const double arg = std::fabs(in->consts[i - 1]) * coord_bound * (1.0 + 1e-9);
+    if (arg < kSrcTrigFastMax / 2) {  // (a NaN constant fails the comparison)
+      fast[i] = 1;
+      ++proven;
+    }
+  }
+  return proven;
+}
+
+template <typename T>
+int src_convert_proven(const tfem_source_program *in, double coord_bound, SrcProgram<T> *out) {
+  const int st = src_convert<T>(in, out);
+  if (st != TFEM_OK || sizeof(T) != 8) return st;
+  uint8_t fast[kSrcMaxOps];
+  if (src_trig_proof(in, coord_bound, fast) == 0) return st;
+  for (int i = 0; i < in->n_ops; ++i)
+    if (fast[i]) {
+      const uint32_t op = in->ops[i] == TFEM_SRC_SIN ? kSrcSinProven : kSrcCosProven;
+      out->opw[i >> 2] = (out->opw[i >> 2] & ~(0xFFu << (8 * (i & 3)))) | (op << (8 * (i & 3)));
+    }
+  return st;
+}
+template int src_convert_proven<double>(const tfem_source_program *, double, SrcProgram<double> *);
+template int src_convert_proven<float>(const tfem_source_program *, double, SrcProgram<float> *);
 
 namespace {
 
@@ -147,6 +184,15 @@ int run_source_eval(const void *coords, const void *conn, int64_t n_elems, int q
 extern "C" {
 
 int tfem_source_validate(const tfem_source_program *program) { return tfem::src_validate(program); }
+
+int tfem_source_trig_proof(const tfem_source_program *program, double max_abs_coord, uint8_t *fast_out) {
+  if (!fast_out) return 0;
+  uint8_t fast[tfem::kSrcMaxOps] = {};
+  int proven = 0;
+  if (program && tfem::src_validate(program) == TFEM_OK) proven = tfem::src_trig_proof(program, max_abs_coord, fast);
+  std::memcpy(fast_out, fast, sizeof(fast));
+  return proven;
+}
 
 int tfem_source_eval(const void *coords, int real_bytes, const void *conn, int idx_bytes,
                      int64_t n_elems, int64_t n_verts, int quad_order,

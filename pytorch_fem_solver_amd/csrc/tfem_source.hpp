@@ -39,6 +39,19 @@ int src_validate(const tfem_source_program *in);
 // Most values a valid program holds at any time (1 .. TFEM_SOURCE_STACK); 0 for an invalid one.
 int src_depth(const tfem_source_program *in);
 
+// Operations of the DEVICE copy only (no caller's program holds them: src_validate refuses them):
+// SIN / COS whose every argument the host has proven to lie below kSrcTrigFastMax, so that the
+// interpreter skips the range test of every value (src_trig_proof).  The wide interpreter of the
+// fp64 launches knows them; src_convert emits them only when it is told a coordinate bound.
+constexpr int kSrcSinProven = TFEM_SRC_OP_COUNT, kSrcCosProven = TFEM_SRC_OP_COUNT + 1;
+// fast[i] = 1 where operation i is a SIN / COS of the coordinate push in front of it (constant c)
+// and |c| coord_bound (1 + 1e-9) < kSrcTrigFastMax / 2; returns how many.  coord_bound: every
+// |x|, |y| the launch can meet (the integration points are convex combinations of the vertices).
+int src_trig_proof(const tfem_source_program *in, double coord_bound, uint8_t (&fast)[kSrcMaxOps]);
+// src_convert with the proven SIN / COS replaced (T = double; float launches take sinf / cosf anyway)
+template <typename T>
+int src_convert_proven(const tfem_source_program *in, double coord_bound, SrcProgram<T> *out);
+
 #if defined(__HIPCC__)
 
 template <typename T>
@@ -424,9 +437,14 @@ __device__ __forceinline__ void src_run_wide(const SrcLanes<T> &prog, const T *c
     const uint32_t op = uint32_t(__builtin_amdgcn_readlane(int(prog.op), pc));
     const T c = src_lane_const<T>(prog, pc);
     if (op <= TFEM_SRC_PUSH_C) {  // a push moves the top entry down -- when there is one
+      // (the empty asm keeps the moves behind the wave-uniform branch: left alone, hipcc turned the
+      // two-element pass's into 4 N selects that also run for a push onto the empty stack)
       if (depth > 0) {
 #pragma unroll
-        for (int i = 0; i < N; ++i) s1[i] = s0[i];
+        for (int i = 0; i < N; ++i) {
+          s1[i] = s0[i];
+          asm volatile("" : "+v"(s1[i]));
+        }
       }
       depth = __builtin_amdgcn_readfirstlane(depth + 1);
     } else if (op <= TFEM_SRC_DIV_R) {
@@ -491,6 +509,13 @@ __device__ __forceinline__ void src_run_wide(const SrcLanes<T> &prog, const T *c
       }
       case TFEM_SRC_SIN: src_sin_scaled<T, N>(s0, c); break;
       case TFEM_SRC_COS: src_cos_scaled<T, N>(s0, c); break;
+      // proven on the host for the whole launch (src_trig_proof): no range test of the N values
+      case kSrcSinProven:
+        if constexpr (sizeof(T) == 8) { TFEM_SRC_SET(src_sin_fast_scaled(t, c)) } else { src_sin_scaled<T, N>(s0, c); }
+        break;
+      case kSrcCosProven:
+        if constexpr (sizeof(T) == 8) { TFEM_SRC_SET(src_cos_fast_scaled(t, c)) } else { src_cos_scaled<T, N>(s0, c); }
+        break;
       case TFEM_SRC_EXP:
         if constexpr (sizeof(T) == 8) { TFEM_SRC_WIDE_APPLY(s0, exp) } else { TFEM_SRC_WIDE_APPLY(s0, expf) }
         TFEM_SRC_SET(c * t)
