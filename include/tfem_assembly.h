@@ -562,6 +562,28 @@ int tfem_p1_apply_rings_field(const void *coords, int real_bytes, int64_t n_vert
                               double alpha, double beta, const void *kappa, int kappa_nq,
                               const void *c, int c_nq, int64_t n_elems, const void *plan_device,
                               const int64_t *plan_layout_host, const void *u, void *y, void *stream);
+/* Y = K U of the same operator for n_vec vectors at once: U and Y (DEVICE, n_verts x n_vec reals each,
+ * ROW-major as for tfem_p1_apply_rings_multi; the plan's vertex numbering) must not overlap; every
+ * entry of Y is written once (0 for a vertex without elements).  The values of a tile's elements are
+ * read and reduced once for a pass of up to 8 columns (4 with 15-slot records; the widest width whose
+ * LDS, ((2 + width) * lds_vert + (7 with a mass term, else 1) * lds_elem) * real_bytes, fits 64 KB),
+ * a larger n_vec is served in several passes over column ranges; column j of Y is bit for bit what
+ * tfem_p1_apply_rings_field gives for column j of U.  n_vec >= 1 of any size within the 32-bit extent
+ * (n_vec = 1 IS tfem_p1_apply_rings_field); u == NULL is an error here (the diagonal has one column:
+ * tfem_p1_apply_rings_field).  Refused before anything is launched, Y untouched, in this order:
+ * real_bytes not 4 or 8, a NULL layout, negative sizes, n_vec < 1, u NULL, both fields NULL, *_nq
+ * neither 1 nor Q (TFEM_ERR_INVALID_ARGUMENT); an extent n_verts * n_vec * real_bytes or n_elems *
+ * *_nq * real_bytes >= 2^32 (TFEM_ERR_INDEX_RANGE); U and Y overlapping anywhere in the block
+ * (TFEM_ERR_INVALID_ARGUMENT); plans with long rows, plans whose tiles do not fit the element stage
+ * (layout[18] == 0, layout[17] > 768), plans whose largest tile needs more than 64 KB of LDS for two
+ * columns -- the caller applies such a plan column by column --, unknown integration orders
+ * (TFEM_ERR_UNSUPPORTED).  Empty plans succeed and launch nothing.  No allocation, no
+ * synchronisation. */
+int tfem_p1_apply_rings_field_multi(const void *coords, int real_bytes, int64_t n_verts, int quad_order,
+                                    double alpha, double beta, const void *kappa, int kappa_nq,
+                                    const void *c, int c_nq, int64_t n_elems, const void *plan_device,
+                                    const int64_t *plan_layout_host, const void *u, void *y,
+                                    int64_t n_vec, void *stream);
 /* The derivative of sum_cols g^T K u with respect to the values (the backward of the apply launch in
  * kappa and c; abstract_basis.py:74-93 differentiated in the coefficient of the integrand), element
  * form, one lane per element:

@@ -240,6 +240,11 @@ SIGNATURES = {
         [c_void_p, c_int, c_int64, c_int, c_double, c_double, c_void_p, c_int, c_void_p, c_int, c_int64,
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    "tfem_p1_apply_rings_field_multi": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_double, c_double, c_void_p, c_int, c_void_p, c_int, c_int64,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
+    ),
     "tfem_p1_field_adjoint": (
         c_int,
         [c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_void_p, c_void_p, c_int64,

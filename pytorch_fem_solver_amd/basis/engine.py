@@ -1323,12 +1323,13 @@ class AssemblyEngine:
     #: LDS a launch over a ring plan may ask for (csrc/tfem_rings_field.hip refuses above it)
     FIELD_LDS_LIMIT = 64 * 1024
 
-    def field_refusal(self, beta, mode):
+    def field_refusal(self, beta, mode, k=1):
         """Why the coefficient-data launches (csrc/tfem_rings_field.hip) do not take this basis, or
         None when they do: P1 on one mesh with a ring plan (kernel "auto" / "rings") without long
         rows, whose tiles fit the element stage and, for the launch's ``mode`` ("apply", "diag",
         "store") with or without a mass term, 64 KB of LDS -- the launch's own refusals, known here
-        before anything is launched."""
+        before anything is launched.  k >= 2 ("apply" only): the block launch
+        (csrc/tfem_rings_field_multi.hip) on k columns, whose narrowest pass stages two columns."""
         if not self.may_apply_matrix_free():
             if self.kernel not in ("auto", "rings"):
                 return f"TFEM_KERNEL={self.kernel} selects a path without the ring plan"
@@ -1345,12 +1346,14 @@ class AssemblyEngine:
         if z[18] == 0:
             return "a tile of the ring plan has more elements than the launch stages"
         rb = self.real_bytes
-        if max(z[1] * z[5], self.n_elems * self.n_quad, 2 * self.n_dofs) * rb >= 1 << 32:
+        if max(z[1] * z[5], self.n_elems * self.n_quad, max(2, k) * self.n_dofs) * rb >= 1 << 32:
             return "an array beyond the launch's 32-bit extents"
         stage = 4 * (64 * (z[6] + 1) + 2) if mode == "store" else 0
-        lds = rb * ((3 if mode == "apply" else 2) * ((z[3] + 1) & ~1) + stage + (7 if beta != 0.0 else 1) * max(z[17], 1))
+        cols = 2 + 2 if k > 1 else 3 if mode == "apply" else 2  # coordinates and the staged columns per vertex
+        lds = rb * (cols * ((z[3] + 1) & ~1) + stage + (7 if beta != 0.0 else 1) * max(z[17], 1))
         if lds > self.FIELD_LDS_LIMIT:
-            return f"the {mode} launch needs {lds} bytes of LDS for this plan, more than {self.FIELD_LDS_LIMIT}"
+            what = "block launch on two columns" if k > 1 else f"{mode} launch"
+            return f"the {what} needs {lds} bytes of LDS for this plan, more than {self.FIELD_LDS_LIMIT}"
         return None
 
     def _field_args(self, fields):
@@ -1387,16 +1390,26 @@ class AssemblyEngine:
     def _apply_rings_field(self, alpha, beta, fields, u, out=None):
         """One tfem_p1_apply_rings_field launch in the ENGINE's numbering: K u of the form with
         coefficient data without its CSR values, u None: the diagonal.  A block (n_dofs, k), k >= 2,
-        goes column by column (the same launch per column), result (n_dofs, k)."""
+        is ONE tfem_p1_apply_rings_field_multi call: the values of a tile's elements are read and
+        reduced once per pass of columns, every column bit for bit the single launch's; result
+        (n_dofs, k).  A plan whose tiles leave no room in LDS for two columns goes column by column
+        through the single launch."""
         why = self.field_refusal(beta, "apply" if u is not None else "diag")
         if why is not None:
             raise NotImplementedError(f"the coefficient-data operator: {why}")
         if _is_block(u):
-            u = u.to(self.device, self.dtype)
+            u = u.to(self.device, self.dtype).contiguous()  # row-major: a vertex's k values are consecutive
             if u.shape[0] != self.n_dofs:
                 raise ValueError(f"apply: u has {u.shape[0]} rows, the operator {self.n_dofs} columns")
             k = int(u.shape[1])
-            y = self._output(out, self.n_dofs * k, "operator result").view(self.n_dofs, k)
+            y = self._output(out, self.n_dofs * k, "operator result")
+            if y.data_ptr() == u.data_ptr():
+                raise ValueError("apply: out must not be u")
+            if k > 1 and self.field_refusal(beta, "apply", k) is None:
+                with torch.cuda.device(self.device):
+                    self._apply_launch(alpha, beta, u, y, fields=fields, k=k)()
+                return y.view(self.n_dofs, k)
+            y = y.view(self.n_dofs, k)
             for j in range(k):
                 y[:, j] = self._apply_rings_field(alpha, beta, fields, u[:, j])
             return y
@@ -1461,8 +1474,9 @@ class AssemblyEngine:
         ONCE (the loop of sparse.fused_conjugate_gradients applies the same two buffers every
         iteration): the returned callable only enqueues, on the stream that is current NOW.  u and
         y: contiguous device tensors of this engine's dtype, (n_dofs,) or (n_dofs, k); P1 takes a
-        block in one call (tfem_p1_apply_rings_multi, with `programs` tfem_p1_apply_rings_coef_multi),
-        the P2 launch and the coefficient-data launch (`fields`) go column by column through a
+        block in one call (tfem_p1_apply_rings_multi, with `programs` tfem_p1_apply_rings_coef_multi,
+        with `fields` tfem_p1_apply_rings_field_multi); the P2 launch, and the coefficient-data launch
+        on a plan whose tiles leave no room in LDS for two columns, go column by column through a
         contiguous pair of columns."""
         for t in (u, y):
             if t.dtype != self.dtype or t.device != self.device or not t.is_contiguous() or t.shape[0] != self.n_dofs:
@@ -1470,7 +1484,7 @@ class AssemblyEngine:
         if u.shape != y.shape or u.data_ptr() == y.data_ptr():
             raise ValueError("prepared apply: u and y must be two tensors of one shape")
         k = int(u.shape[1]) if _is_block(u) else 1
-        multi = k > 1 and self.poly_order == 1 and fields is None
+        multi = k > 1 and self.poly_order == 1 and (fields is None or self.field_refusal(beta, "apply", k) is None)
         if k > 1 and not multi:
             u_col, y_col = (torch.empty(self.n_dofs, dtype=self.dtype, device=self.device) for _ in range(2))
             one = self._prepared_apply(alpha, beta, u_col, y_col, programs, fields)
@@ -1487,7 +1501,7 @@ class AssemblyEngine:
     def _apply_launch(self, alpha, beta, u, y, programs=None, k=1, fields=None):
         """THE call of the matrix-free apply launches (tfem_p1_apply_rings, _multi for k >= 2,
         _coef with `programs` = (kappa, c), _coef_multi with both, _field with `fields` = (kappa, c)
-        values, tfem_p2_apply_rows on P2) with its arguments converted:
+        values, _field_multi with both, tfem_p2_apply_rows on P2) with its arguments converted:
         y = K u in the engine's numbering, u None: the diagonal; u and y as the callers have
         checked them.  The returned callable enqueues on the stream that is current now."""
         d = self._inputs()
@@ -1510,10 +1524,13 @@ class AssemblyEngine:
             where = (_native.ptr(plan["blob"]), c_void_p(plan["layout"].ctypes.data))
             head = (*head, self.n_dofs, self.quad_order, *scale)
             if fields is not None:
+                data = (*head, *self._field_args(fields), *where, *tail)
                 if k > 1:
-                    raise NotImplementedError("the coefficient-data launch applies one vector")
-                fn = self.lib.tfem_p1_apply_rings_field
-                args = (*head, *self._field_args(fields), *where, *tail, stream)
+                    fn = self.lib.tfem_p1_apply_rings_field_multi
+                    args = (*data, k, stream)
+                else:
+                    fn = self.lib.tfem_p1_apply_rings_field
+                    args = (*data, stream)
             elif programs is not None:
                 coef = (*head, self._program_ref(programs[0]), self._program_ref(programs[1]), *where, *tail)
                 if k > 1:

@@ -34,118 +34,16 @@
 // k_p1_field_adjoint: the derivative of g^T K u with respect to the values, element form (modelled on
 // k_p1_residual_backward): one lane per element, g and u gathered at its three vertices for every
 // column, summed over the columns in registers; every entry written once.
-#include "tfem_rings_coef.hpp"
+#include "tfem_rings_field.hpp"
 
 namespace tfem {
 
 constexpr int kFieldApply = 0, kFieldDiag = 1, kFieldStore = 2;
-constexpr size_t kFieldLdsLimit = 64 * 1024;
-
-template <typename T>
-struct FieldArgs {
-  const T *u;
-  T *y;
-  const T *kappa, *c;  // (n_elems, kappa_nq) / (n_elems, c_nq) values
-  unsigned u_bytes, y_bytes, kappa_bytes, c_bytes;
-  int kappa_nq, c_nq;  // Q: a value per integration point; 1: one per element; 0: the constant 1
-  T alpha, beta;
-};
-
-template <typename T>
-struct FieldLaunch {  // the kernel's only parameter
-  RingArgs<T> a;
-  FieldArgs<T> b;
-};
-
-// The 12-bit slot codes of a row in fan order, one per pop (packed as the plan packs them).
-template <int SLOTS>
-struct CodeCursor {
-  static constexpr int kWords = (12 * SLOTS + 31) / 32;  // 3 or 6
-  uint32_t w[kWords];
-  __device__ __forceinline__ uint32_t code() const { return w[0] & 0xFFFu; }
-  __device__ __forceinline__ void next() {
-#pragma unroll
-    for (int j = 0; j + 1 < kWords; ++j) w[j] = (w[j] >> 12) | (w[j + 1] << 20);
-    w[kWords - 1] >>= 12;
-  }
-};
-
-// Reals per staged element: wk, then m00 m01 m02 m11 m12 m22.
-template <bool MASS>
-constexpr int field_elem_reals() { return MASS ? 7 : 1; }
-
-// The row of local vertex `lv` from the element table `etab`: ring_row_coef with the per-triangle
-// numbers read from LDS instead of evaluated.  emit(live, id, pos, value) once per slot, the diagonal
-// in diag; kmax: the largest fan of the wave (wave-uniform).
-template <typename T, int SLOTS, bool MASS, typename Emit>
-__device__ __forceinline__ void ring_row_field(const RingRec<SLOTS> &rec, CodeCursor<SLOTS> &ec, uint32_t lv,
-                                               const T *xy, const T *etab, int kmax, T &diag, Emit &&emit) {
-  constexpr int ES = field_elem_reals<MASS>();
-  const int k = rec.k();
-  RecCursor<SLOTS> cur(rec);
-  T xv, yv, pcx, pcy;
-  lds_xy(xy, lv, xv, yv);
-  const uint32_t id0 = cur.id();
-  const int pos0 = cur.at();
-  lds_xy(xy, id0, pcx, pcy);
-  T sum_st = T(0), dmass = T(0), carry = T(0), wrapv = T(0), e0 = T(0);
-#pragma unroll 1
-  for (int i = 0; i < kmax; ++i) {
-    const uint32_t id_i = cur.id();
-    const int pos_i = cur.at();
-    const uint32_t flag = i < k ? cur.flag() : 0u;
-    cur.next();
-    const uint32_t code = ec.code();
-    ec.next();
-    // neighbour behind slot i: slot i + 1, or slot 0 where the fan closes
-    const uint32_t idn = (i + 1 < SLOTS && i + 1 != k) ? cur.id() : id0;
-    T pnx, pny;
-    lds_xy(xy, idn, pnx, pny);
-    const T ecx = pcx - xv, ecy = pcy - yv, enx = pnx - xv, eny = pny - yv;
-    const T qc = ecx * ecx + ecy * ecy, qn = enx * enx + eny * eny;
-    const T p = ecx * enx + ecy * eny;
-    const T cross = ecx * eny - ecy * enx;  // +- the signed determinant (element_tri.py:139)
-    // the slot's element in the tile's table; a slot without a triangle reads entry 0 and discards it
-    const bool none = flag == 0u || code == 0xFFFu;
-    const uint32_t el = none ? 0u : (code & 0x3FFu);
-    const uint32_t loc = none ? 0u : (code >> 10);
-    const T *ep = etab + el * unsigned(ES);
-    const T wk = ep[0];
-    const T cs = flag_weight<T>(wk, flag) * fast_rcp<T>(flag ? cross : T(1));
-    T here = cs * (p - qn), next = cs * (p - qc);  // to column n_i, to column n_next
-    sum_st = sum_st + (here + next);
-    if (MASS) {
-      // m[loc][loc], m[loc][loc + 1], m[loc][loc + 2] in the table's order (1 + index of i <= j)
-      const T mvv = ep[(0x641u >> (4u * loc)) & 0xFu];
-      const T ma = ep[(0x352u >> (4u * loc)) & 0xFu];
-      const T mb = ep[(0x523u >> (4u * loc)) & 0xFu];
-      // flag 1: the element holds (v, n_i, n_next): n_i is its local vertex loc + 1; flag 2: loc + 2
-      const T mvi = (flag & 2u) ? mb : ma, mvn = (flag & 2u) ? ma : mb;
-      // selects, not products with a zero determinant: a discarded table entry may be anything
-      const T sdet = flag_weight<T>(T(1), flag) * cross;
-      here = here + (flag ? mvi * sdet : T(0));
-      next = next + (flag ? mvn * sdet : T(0));
-      dmass = dmass + (flag ? mvv * sdet : T(0));
-    }
-    const T entry = here + carry;
-    carry = next;
-    wrapv = i + 1 == k ? next : wrapv;  // the closing triangle's second share belongs to slot 0
-    if (i == 0)
-      e0 = here;
-    else
-      emit(i < k, id_i, pos_i, entry);
-    pcx = pnx;
-    pcy = pny;
-  }
-  emit(k > 0, id0, pos0, e0 + wrapv);
-  diag = dmass - sum_st;
-}
 
 template <typename T, int SLOTS, bool MASS, bool CHUNK, int QL, int MODE>
 __global__ __launch_bounds__(kRingBlock) void k_p1_field_rows(const FieldLaunch<T> L) {
   const RingArgs<T> &a = L.a;
   const FieldArgs<T> &b = L.b;
-  constexpr int ES = field_elem_reals<MASS>();
   constexpr int kEW = CodeCursor<SLOTS>::kWords;
   extern __shared__ __attribute__((aligned(16))) unsigned char ring_smem[];
   T *xy = reinterpret_cast<T *>(ring_smem);  // [2 * lds_vert]
@@ -169,72 +67,19 @@ __global__ __launch_bounds__(kRingBlock) void k_p1_field_rows(const FieldLaunch<
   const ring_rsrc_t r_kappa = ring_rsrc(b.kappa, b.kappa_bytes);
   const ring_rsrc_t r_c = ring_rsrc(b.c, b.c_bytes);
   constexpr unsigned kRecBytes = unsigned(4 * RingRec<SLOTS>::kWords);
-  constexpr unsigned kNone = 0x3FFFFFFu;  // index behind every array: buffer loads give 0
-  constexpr unsigned kBehind = 0xFFFFFFF0u;  // byte offset behind every value array
+  constexpr unsigned kNone = kFieldNone;
   constexpr int kSpare = 64 * (SLOTS + 1);  // the stage's spare entries (ring_stage_entries)
 
   auto tile_at = [&](int j) { return (j < per && xcd * per + j < a.n_tiles) ? xcd * per + j : -1; };
-  // vertex ids of a tile: the lane's own row and halo vertex number tid (as k_p1_apply_rows)
+  // the ids and values of a tile: tfem_rings_field.hpp
   auto load_ids = [&](const RingDesc &d, unsigned &g_own, unsigned &g_halo) {
-    const int r = d.row0 + lane;
-    if (CHUNK)
-      g_own = unsigned(d.gid0 + lane);
-    else
-      g_own = __builtin_amdgcn_raw_buffer_load_b32(
-          r_plan, a.off_gid + (r < d.row1 ? unsigned(d.vert_off + r) : kNone) * 4u, 0, 0);
-    const int h = d.n_own + tid;
-    g_halo = __builtin_amdgcn_raw_buffer_load_b32(
-        r_plan, a.off_gid + (h < d.n_vert ? unsigned(d.vert_off + h) : kNone) * 4u, 0, 0);
+    field_load_ids<T, CHUNK>(a, r_plan, d, tid, lane, g_own, g_halo);
   };
-  // element ids of a tile stored as a list (desc[18] = 0): position tid + 256 j of the list
-  auto load_eids = [&](const RingDesc &d, unsigned (&e)[kRingElemPerLane]) {
-    if (d.elem_mode) return;  // runs of consecutive ids: nothing to fetch
-#pragma unroll
-    for (int j = 0; j < kRingElemPerLane; ++j) {
-      const int l = tid + j * kRingBlock;
-      e[j] = __builtin_amdgcn_raw_buffer_load_b32(
-          r_plan, a.off_telems + (l < d.n_elem ? unsigned(d.elem_off + l) : kNone) * 4u, 0, 0);
-    }
-  };
-  // ... and of a tile stored as runs (desc[18] = 1): from the first ids of the runs and the list
-  // positions they end at (16 scalars of the plan), as load_fq derives them
-  auto run_eids = [&](const RingDesc &d, unsigned (&e)[kRingElemPerLane]) {
-    if (!d.elem_mode) return;
-    ring_const_i32 rg = (ring_const_i32)(uintptr_t)(a.plan + a.off_telems + 4u * unsigned(d.elem_off));
-    int first[kRingElemRuns], upto[kRingElemRuns];
-#pragma unroll
-    for (int r = 0; r < kRingElemRuns; ++r) {
-      first[r] = rg[r];
-      upto[r] = rg[kRingElemRuns + r];
-    }
-#pragma unroll
-    for (int j = 0; j < kRingElemPerLane; ++j) {
-      const int l = tid + j * kRingBlock;
-      int id = first[0] + l;
-#pragma unroll
-      for (int r = 1; r < kRingElemRuns; ++r) id = l >= upto[r - 1] ? first[r] + (l - upto[r - 1]) : id;
-      e[j] = unsigned(id);
-    }
-  };
-  auto load_real = [&](ring_rsrc_t r, unsigned byte) {
-    if constexpr (sizeof(T) == 8) {
-      const ru32x2 v{__builtin_amdgcn_raw_buffer_load_b32(r, byte, 0, 0),
-                     __builtin_amdgcn_raw_buffer_load_b32(r, byte + 4u, 0, 0)};
-      return __builtin_bit_cast(double, v);
-    } else {
-      return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte, 0, 0));
-    }
-  };
-  auto load_u = [&](unsigned g) { return load_real(r_u, g * unsigned(sizeof(T))); };
-  // the values of one element: Q of them, or the element's one value for every point, or 1
+  auto load_eids = [&](const RingDesc &d, unsigned (&e)[kRingElemPerLane]) { field_load_eids<T>(a, r_plan, d, tid, e); };
+  auto run_eids = [&](const RingDesc &d, unsigned (&e)[kRingElemPerLane]) { field_run_eids<T>(a, d, tid, e); };
+  auto load_u = [&](unsigned g) { return field_load_real<T>(r_u, g * unsigned(sizeof(T))); };
   auto load_vals = [&](ring_rsrc_t r, int nq, unsigned id, bool live, T (&v)[QL]) {
-    if (nq == QL) {
-      ring_load_fq<T, QL>(r, live ? id * unsigned(QL * sizeof(T)) : kBehind, v);
-    } else {
-      const T one = nq == 1 ? load_real(r, live ? id * unsigned(sizeof(T)) : kBehind) : T(1);
-#pragma unroll
-      for (int q = 0; q < QL; ++q) v[q] = one;
-    }
+    field_load_vals<T, QL>(r, nq, id, live, v);
   };
 
   int j = int(blockIdx.x >> 3);
@@ -302,33 +147,7 @@ __global__ __launch_bounds__(kRingBlock) void k_p1_field_rows(const FieldLaunch<
       if (MODE == kFieldApply) us[h] = halo_u;
     }
     // wk and m_ij of the elements just loaded -> LDS, by their position in the tile's list
-#pragma unroll
-    for (int e = 0; e < kRingElemPerLane; ++e) {
-      const int l = tid + e * kRingBlock;
-      if (l < n_elem) {
-        T *ep = etab + l * ES;
-        T w = T(0);
-#pragma unroll
-        for (int q = 0; q < QL; ++q) w = w + a.hw[q] * kv[e][q];
-        ep[0] = b.alpha * w;
-        if (MASS) {
-          T f[QL];
-#pragma unroll
-          for (int q = 0; q < QL; ++q) f[q] = a.hw[q] * cv[MASS ? e : 0][q];
-          int at = 1;
-#pragma unroll
-          for (int i0 = 0; i0 < 3; ++i0) {
-#pragma unroll
-            for (int i1 = i0; i1 < 3; ++i1) {
-              T s = T(0);
-#pragma unroll
-              for (int q = 0; q < QL; ++q) s = s + (f[q] * a.lam[i0][q]) * a.lam[i1][q];
-              ep[at++] = b.beta * s;
-            }
-          }
-        }
-      }
-    }
+    TFEM_FIELD_FILL_TABLE(T, MASS, QL, a, b, etab, tid, n_elem, kv, cv)
     __syncthreads();
     const uint32_t lv = unsigned(own ? r : 0);
     const int k = rec.k();
@@ -416,26 +235,16 @@ static int launch_field(const TriTables &tables, const void *coords, int64_t n_v
     return fail(TFEM_ERR_UNSUPPORTED, "a tile of this ring plan has %lld elements: the coefficient-data launch "
                 "stages at most %d", (long long)z[17], kRingElemPerLane * kRingBlock);
   FieldLaunch<T> K;
-  int st = ring_args_init<T>(tables, z, coords, plan, n_verts, alpha, beta, K.a);
+  int st = field_args_init<T>(tables, coords, n_verts, alpha, beta, kappa, kappa_nq, c, c_nq, n_elems, plan, z, K);
   if (st != TFEM_OK) return st;
   RingArgs<T> &a = K.a;
   FieldArgs<T> &b = K.b;
-  std::memset(&b, 0, sizeof(b));
-  for (int i = 0; i < 3; ++i)
-    for (int q = 0; q < tables.nq; ++q) a.lam[i][q] = T(tables.lam[q][i]);
-  for (int q = 0; q < tables.nq; ++q) a.hw[q] = T(tables.hw[q]);
   // the CSR values: bounded by rows x longest row, as in the coefficient-program launch
-  const int64_t bytes[4] = {n_verts * int64_t(sizeof(T)),
-                            mode == kFieldStore ? z[1] * z[5] * int64_t(sizeof(T)) : 0,
-                            kappa ? n_elems * kappa_nq * int64_t(sizeof(T)) : 0,
-                            c ? n_elems * c_nq * int64_t(sizeof(T)) : 0};
-  st = check_extents("ring kernel", bytes, 4);
+  const int64_t bytes[2] = {n_verts * int64_t(sizeof(T)), mode == kFieldStore ? z[1] * z[5] * int64_t(sizeof(T)) : 0};
+  st = check_extents("ring kernel", bytes, 2);
   if (st != TFEM_OK) return st;
   const bool mass = beta != 0.0, chunk = z[13] != 0;
   const int slots = int(z[6]);
-  a.off_elems = unsigned(z[15]);
-  a.off_telems = unsigned(z[16]);
-  a.lds_elem = int(std::max<int64_t>(z[17], 1));
   const size_t lds = size_t((mode == kFieldApply ? 3 : 2) * a.lds_vert) * sizeof(T) +
                      (mode == kFieldStore ? size_t(kRingWaves) * size_t(64 * (slots + 1) + 2) * sizeof(T) : 0) +
                      size_t(mass ? 7 : 1) * size_t(a.lds_elem) * sizeof(T);
@@ -447,14 +256,6 @@ static int launch_field(const TriTables &tables, const void *coords, int64_t n_v
   b.y = static_cast<T *>(y);
   b.u_bytes = mode == kFieldApply ? unsigned(bytes[0]) : 0u;
   b.y_bytes = mode == kFieldStore ? 0u : unsigned(bytes[0]);
-  b.kappa = static_cast<const T *>(kappa);
-  b.c = static_cast<const T *>(c);
-  b.kappa_bytes = unsigned(bytes[2]);
-  b.c_bytes = unsigned(bytes[3]);
-  b.kappa_nq = kappa ? kappa_nq : 0;
-  b.c_nq = c ? c_nq : 0;
-  b.alpha = T(alpha);
-  b.beta = T(beta);
   a.vals = static_cast<T *>(vals);
   a.vals_bytes = mode == kFieldStore ? unsigned(bytes[1]) : 0u;
   a.plain_stores = 1;  // the matrix alone: the store policy of the matrix-only ring launch

@@ -516,17 +516,19 @@ class FormOperator:
     the programs are evaluated per triangle inside the launch), or coefficient DATA -- values of kappa
     and c at the integration points or per element (``basis.coefficient``; tfem_p1_apply_rings_field:
     the values of a tile's elements are read once per tile and reduced in LDS); ``matvec`` is then also
-    differentiable in the values (tfem_p1_field_adjoint), blocks go column by column.  Otherwise the operator
+    differentiable in the values (tfem_p1_field_adjoint).  Otherwise the operator
     wraps the CSRMatrix of today's assembly and applies it with tfem_csr_spmv (P2, fractures, any
     other integrand, meshes without a ring plan); the interface and the results are the same.
     Vectors are taken and returned in the caller's DoF numbering, of shape (N,) or (N, 1); a block
     (N, k) of k >= 2 vectors gives (N, k): matrix-free on P1 by ONE call that forms the rows of K
     once for the k columns (tfem_p1_apply_rings_multi; with coefficient programs
-    tfem_p1_apply_rings_coef_multi, which evaluates the programs once for the k columns), the
+    tfem_p1_apply_rings_coef_multi, which evaluates the programs once for the k columns; with
+    coefficient data tfem_p1_apply_rings_field_multi, which reads and reduces the values once for the
+    k columns -- also the forward and the ``K g`` of the backward of a differentiable ``matvec``), the
     operator that wraps the CSR by ONE tfem_csr_spmm launch that reads the matrix once for the k
     columns (``CSRMatrix.matvec``; also the backward of ``matvec`` in the block, and every iteration
-    of the block CG loops), the P2 matrix-free operator and the operator with coefficient data by
-    their single-vector launch once per column.
+    of the block CG loops), the P2 matrix-free operator by its single-vector launch once per column
+    (as the operator with coefficient data on a plan whose tiles leave no room in LDS for two columns).
 
     ``layout="matrix_free"`` is the strict request: the plan is built at the call, the operator it
     returns is matrix-free from the start (``matrix_free`` True), and a basis or form without the
