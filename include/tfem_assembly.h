@@ -707,6 +707,23 @@ int tfem_p2_apply_rows(const void *coords, int real_bytes, int quad_order, doubl
                        const void *plan_device, const int64_t *plan_layout_host,
                        const int32_t *colind, int64_t nnz, const void *u, void *y, int64_t n_dofs,
                        void *stream);
+/* Y = (alpha * stiffness + beta * mass) U of the same operator for n_vec vectors at once: U and Y
+ * (DEVICE, n_dofs x n_vec reals each, ROW-major: the n_vec values of a DoF are consecutive, the
+ * layout of tfem_p1_apply_rings_multi; the plan's DoF numbering) must not overlap; every entry of Y
+ * is written once.  The records, colind, the coordinates and the entries of a row are read and
+ * formed once per pass of up to 4 columns, a larger n_vec is served in several passes over column
+ * ranges; the long vertex rows take every column in one launch.  real_bytes 4: one launch per kind
+ * of row reads them once and forms the row once per column (what the bits below need in fp32).
+ * Column c of Y has the bits that tfem_p2_apply_rows gives for column c.  n_vec >= 1 (n_vec = 1 IS the tfem_p2_apply_rows launch);
+ * u == NULL on a non-empty plan is an error here (the diagonal has one column: tfem_p2_apply_rows).
+ * Everything tfem_p2_apply_rows refuses is refused in the same way; in addition n_vec < 1 and U
+ * overlapping Y anywhere in n_dofs * n_vec * real_bytes give TFEM_ERR_INVALID_ARGUMENT, and that
+ * extent reaching 0xFFFFFF00 bytes gives TFEM_ERR_INDEX_RANGE.  Nothing is launched and Y is not
+ * touched after a refusal; an empty plan launches nothing.  No allocation, no synchronisation. */
+int tfem_p2_apply_rows_multi(const void *coords, int real_bytes, int quad_order, double alpha,
+                             double beta, const void *plan_device, const int64_t *plan_layout_host,
+                             const int32_t *colind, int64_t nnz, const void *u, void *y,
+                             int64_t n_dofs, int64_t n_vec, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * The vector part of the Jacobi-preconditioned CG loop around any of the applies above (the loop

@@ -153,6 +153,11 @@ SIGNATURES = {
         [c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
          c_int64, c_void_p],
     ),
+    "tfem_p2_apply_rows_multi": (
+        c_int,
+        [c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+         c_int64, c_int64, c_void_p],
+    ),
     "tfem_cg_workspace_bytes": (c_int, [c_int64, c_int64]),
     "tfem_cg_constant": (c_int, [c_int]),
     "tfem_cg_start": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p]),

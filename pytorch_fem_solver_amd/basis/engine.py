@@ -1172,20 +1172,23 @@ class AssemblyEngine:
     def _apply_p2_rows(self, alpha, beta, u, out=None):
         """One tfem_p2_apply_rows call in the ENGINE's numbering: (alpha * stiffness + beta * mass) u
         of a P2 basis without the CSR values, u None: the diagonal.  A block (n_dofs, k), k >= 2,
-        goes column by column (the same launch per column), result (n_dofs, k)."""
+        is ONE tfem_p2_apply_rows_multi call (every row of K formed once per pass of columns),
+        result (n_dofs, k)."""
         rows = self.p2_plan()
         if rows is None:
             raise NotImplementedError("the matrix-free P2 operator needs the P2 row plan (a numbering with "
                                       "locality, at most 15 neighbours per vertex)")
         if _is_block(u):
-            u = u.to(self.device, self.dtype)
+            u = u.to(self.device, self.dtype).contiguous()  # row-major: a DoF's k values are consecutive
             if u.shape[0] != self.n_dofs:
                 raise ValueError(f"apply: u has {u.shape[0]} rows, the operator {self.n_dofs} columns")
             k = int(u.shape[1])
-            y = self._output(out, self.n_dofs * k, "operator result").view(self.n_dofs, k)
-            for j in range(k):
-                y[:, j] = self._apply_p2_rows(alpha, beta, u[:, j])
-            return y
+            y = self._output(out, self.n_dofs * k, "operator result")
+            if y.data_ptr() == u.data_ptr():
+                raise ValueError("apply: out must not be u")
+            with torch.cuda.device(self.device):
+                self._apply_launch(alpha, beta, u, y, k=k)()
+            return y.view(self.n_dofs, k)
         if u is not None:
             u = u.to(self.device, self.dtype).reshape(-1).contiguous()
             if u.shape[0] != self.n_dofs:
@@ -1206,7 +1209,7 @@ class AssemblyEngine:
     def apply(self, alpha, beta, u, out=None):
         """(alpha * stiffness + beta * mass) u, matrix-free over the ring plan (P1) or the P2 row
         plan; u and the result (flat, n_dofs) in the caller's numbering, or (n_dofs, k) for k >= 2
-        vectors (P1: in one launch).  ``out``: a preallocated device buffer."""
+        vectors (in one launch).  ``out``: a preallocated device buffer."""
         if self._perm is None:
             return self._apply_rows(alpha, beta, u, out)
         if _is_block(u):
@@ -1473,18 +1476,18 @@ class AssemblyEngine:
         """The matrix-free launch y = K u in the ENGINE's numbering with every argument converted
         ONCE (the loop of sparse.fused_conjugate_gradients applies the same two buffers every
         iteration): the returned callable only enqueues, on the stream that is current NOW.  u and
-        y: contiguous device tensors of this engine's dtype, (n_dofs,) or (n_dofs, k); P1 takes a
-        block in one call (tfem_p1_apply_rings_multi, with `programs` tfem_p1_apply_rings_coef_multi,
-        with `fields` tfem_p1_apply_rings_field_multi); the P2 launch, and the coefficient-data launch
-        on a plan whose tiles leave no room in LDS for two columns, go column by column through a
-        contiguous pair of columns."""
+        y: contiguous device tensors of this engine's dtype, (n_dofs,) or (n_dofs, k); a block is
+        one call (tfem_p1_apply_rings_multi, with `programs` tfem_p1_apply_rings_coef_multi, with
+        `fields` tfem_p1_apply_rings_field_multi, on P2 tfem_p2_apply_rows_multi); only the
+        coefficient-data launch on a plan whose tiles leave no room in LDS for two columns goes column
+        by column through a contiguous pair of columns."""
         for t in (u, y):
             if t.dtype != self.dtype or t.device != self.device or not t.is_contiguous() or t.shape[0] != self.n_dofs:
                 raise ValueError(f"prepared apply: contiguous {self.dtype} tensors of {self.n_dofs} rows on {self.device}")
         if u.shape != y.shape or u.data_ptr() == y.data_ptr():
             raise ValueError("prepared apply: u and y must be two tensors of one shape")
         k = int(u.shape[1]) if _is_block(u) else 1
-        multi = k > 1 and self.poly_order == 1 and (fields is None or self.field_refusal(beta, "apply", k) is None)
+        multi = k > 1 and (self.poly_order == 2 or fields is None or self.field_refusal(beta, "apply", k) is None)
         if k > 1 and not multi:
             u_col, y_col = (torch.empty(self.n_dofs, dtype=self.dtype, device=self.device) for _ in range(2))
             one = self._prepared_apply(alpha, beta, u_col, y_col, programs, fields)
@@ -1501,7 +1504,8 @@ class AssemblyEngine:
     def _apply_launch(self, alpha, beta, u, y, programs=None, k=1, fields=None):
         """THE call of the matrix-free apply launches (tfem_p1_apply_rings, _multi for k >= 2,
         _coef with `programs` = (kappa, c), _coef_multi with both, _field with `fields` = (kappa, c)
-        values, _field_multi with both, tfem_p2_apply_rows on P2) with its arguments converted:
+        values, _field_multi with both, tfem_p2_apply_rows and _multi for k >= 2 on P2) with its
+        arguments converted:
         y = K u in the engine's numbering, u None: the diagonal; u and y as the callers have
         checked them.  The returned callable enqueues on the stream that is current now."""
         d = self._inputs()
@@ -1514,9 +1518,14 @@ class AssemblyEngine:
             if plan is None:
                 raise NotImplementedError("the matrix-free P2 operator needs the P2 row plan")
             colind = self.csr_structure()[1]
-            fn = self.lib.tfem_p2_apply_rows
             args = (*head, self.quad_order, *scale, _native.ptr(plan["blob"]), c_void_p(plan["layout"].ctypes.data),
-                    _native.ptr(colind), int(colind.shape[0]), *tail, self.n_dofs, stream)
+                    _native.ptr(colind), int(colind.shape[0]), *tail, self.n_dofs)
+            if k > 1:
+                fn = self.lib.tfem_p2_apply_rows_multi
+                args = (*args, k, stream)
+            else:
+                fn = self.lib.tfem_p2_apply_rows
+                args = (*args, stream)
         else:
             plan = self.ring_plan() if programs is None else self._coef_rings()
             if plan is None:

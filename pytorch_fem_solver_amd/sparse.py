@@ -527,15 +527,18 @@ class FormOperator:
     k columns -- also the forward and the ``K g`` of the backward of a differentiable ``matvec``), the
     operator that wraps the CSR by ONE tfem_csr_spmm launch that reads the matrix once for the k
     columns (``CSRMatrix.matvec``; also the backward of ``matvec`` in the block, and every iteration
-    of the block CG loops), the P2 matrix-free operator by its single-vector launch once per column
-    (as the operator with coefficient data on a plan whose tiles leave no room in LDS for two columns).
+    of the block CG loops), the P2 matrix-free operator by ONE tfem_p2_apply_rows_multi call that reads
+    the records and colind and forms a row's entries once for the k columns; only the operator with
+    coefficient data on a plan whose tiles leave no room in LDS for two columns runs its
+    single-vector launch once per column.
 
     ``layout="matrix_free"`` is the strict request: the plan is built at the call, the operator it
     returns is matrix-free from the start (``matrix_free`` True), and a basis or form without the
     launch raises NotImplementedError there instead of assembling.  It also serves P2 bases
     (``p2_rows``): ``alpha * stiffness + beta * mass`` over the P2 row plan, every ``matvec`` one
     tfem_p2_apply_rows call (vertex rows, long vertex rows, edge rows) that reads the pattern's
-    column indices but no values; a block goes column by column."""
+    column indices but no values; a block (N, k) is one tfem_p2_apply_rows_multi call, column j with
+    the bits of the single launch on column j."""
 
     def __init__(self, n, dtype, device, assemble, engine=None, alpha=0.0, beta=0.0, symmetric=True,
                  programs=None, p2_rows=False, matrix_free=None, fields=None, field_sources=None):
