@@ -776,6 +776,38 @@ int tfem_cg_direction(void *p, const void *r, const void *inv_diag, const int32_
                       void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The vector part of a geometric multigrid V-cycle on nested P1 spaces (a mesh and its red
+ * refinement; the reference has no multigrid, this stands where its dense solve stops being
+ * possible, abstract_basis.py:114-117,177-195).  All arrays DEVICE; vectors of reals of real_bytes
+ * 4 or 8.  Masks are arrays of reals holding 0 or 1, NULL = all ones.  One launch each, no
+ * allocation, no synchronisation, no atomics: two calls on the same data give the same bits.
+ * smooth:   first != 0: x = w * b (a sweep from the zero guess; ax is not read and may be NULL);
+ *           first == 0: x = x + w * (b - ax), ax = K x from an apply.  w = omega * mask / diag(K),
+ *           prepared by the caller.  n entries each.
+ * restrict_residual: r_c[v] = mask_c[v] * 0.5 * sum_j mask_f[i_j] * (b_f[i_j] - ax_f[i_j]) over
+ *           i_j = idx[ptr[v]] .. idx[ptr[v + 1] - 1], the transposed parent table of the
+ *           refinement: ptr (n_c + 1 int32), idx (2 n_f int32) lists for coarse vertex v the fine
+ *           vertices that name v as a parent, ascending, a vertex kept from the coarse mesh TWICE
+ *           (so every weight of P^T is 0.5).  Eight lanes per row: lane s sums entries s, s + 8, ...
+ *           in order, then the partial sums are added pairwise at distances 4, 2, 1.
+ * prolong_add: x_f[i] = x_f[i] + mask_f[i] * 0.5 * (e_c[parents[2 i]] + e_c[parents[2 i + 1]]),
+ *           parents (n_f x 2 int32) coarse vertex ids.
+ * A product and a sum are rounded separately (no fma).  idx, parents and what they index are read
+ * through bounds-checked buffer accesses: an index outside its array reads 0.
+ * TFEM_ERR_INVALID_ARGUMENT: real_bytes not 4 or 8, a negative size, a NULL array that would be
+ * read or written, the output overlapping an input; TFEM_ERR_INDEX_RANGE: an array of 4 GiB or
+ * more.  Nothing is launched after a refusal; n == 0 (smooth), n_c == 0 (restrict), n_f == 0
+ * (prolong) succeed and launch nothing.
+ * ------------------------------------------------------------------------- */
+int tfem_mg_smooth(void *x, const void *b, const void *ax, const void *w, int real_bytes, int64_t n,
+                   int first, void *stream);
+int tfem_mg_restrict_residual(const int32_t *ptr, const int32_t *idx, const void *mask_c,
+                              const void *mask_f, const void *b_f, const void *ax_f, void *r_c,
+                              int real_bytes, int64_t n_c, int64_t n_f, void *stream);
+int tfem_mg_prolong_add(const int32_t *parents, const void *mask_f, const void *e_c, void *x_f,
+                        int real_bytes, int64_t n_f, int64_t n_c, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Interface exchange of the multi-GPU sharding (DEVICE; the path shards by element
  * range, DoFs on an inter-rank interface are summed with one all-reduce of a packed
  * buffer: SURVEY 8(e); the reference is single-process).  pack: buf (nbuf) is zeroed,

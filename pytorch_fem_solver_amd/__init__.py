@@ -18,6 +18,7 @@ from .element import AbstractElement, ElementLine, ElementTri
 from .mesh import AbstractMesh, FracturesTri, MeshData, MeshesTri, MeshTri
 from .sparse import CSRMatrix, FormOperator
 from .basis.forms import CoefficientField
+from .multigrid import GeometricMultigrid
 
 __all__ = [
     "Basis",
@@ -31,6 +32,7 @@ __all__ = [
     "MeshesTri",
     "CSRMatrix",
     "FormOperator",
+    "GeometricMultigrid",
     "CoefficientField",
     "meshgen",
 ]

@@ -31,6 +31,7 @@ __all__ = [
     "fracture_rectangle",
     "morton_order",
     "permute_mesh",
+    "refine_uniform",
 ]
 
 
@@ -276,3 +277,80 @@ def permute_mesh(mesh: dict, vertex_order=None, triangle_order=None, sort_edges=
                 nb >= 0, old_to_new_t[np.clip(nb, 0, None)], -1
             ).astype(np.int32)
     return out
+
+
+def _neighbors_from_triangles(triangles: np.ndarray, n_vertices: int) -> np.ndarray:
+    """``neighbors`` of a triangle list: entry k is the triangle across the edge opposite corner
+    k, -1 where there is none."""
+    t = triangles.astype(np.int64)
+    n_t = t.shape[0]
+    a, b = t[:, [1, 2, 0]], t[:, [2, 0, 1]]  # the edge opposite corner k, per (triangle, k)
+    keys = (np.minimum(a, b) * n_vertices + np.maximum(a, b)).reshape(-1)
+    order = np.argsort(keys, kind="stable")
+    ks = keys[order]
+    same = ks[1:] == ks[:-1]
+    if same.size > 1 and bool((same[1:] & same[:-1]).any()):
+        raise ValueError("an edge is shared by more than two triangles")
+    neighbors = np.full(3 * n_t, -1, dtype=np.int32)
+    first, second = order[:-1][same], order[1:][same]
+    neighbors[first] = second // 3
+    neighbors[second] = first // 3
+    return neighbors.reshape(n_t, 3)
+
+
+def refine_uniform(mesh: dict):
+    """Red refinement of a triangle-format mesh: ``(fine, parents)``.
+
+    The fine vertices are the coarse vertices and one midpoint per edge; triangle e becomes the
+    triangles 4e .. 4e+3 -- the three corner triangles, then the middle one -- each in the stored
+    orientation of its parent (a clockwise parent has clockwise children).  A coarse edge becomes
+    two edges with its marker, every triangle adds three interior edges with marker 0, a midpoint
+    takes the marker of its edge, ``neighbors`` is rebuilt.  The fine vertices are numbered along
+    the Morton curve (``morton_order``), so every level of a hierarchy has a numbering with
+    locality.  ``parents`` (V_fine, 2) int32, rows in the returned numbering, entries coarse vertex
+    ids: ``(a, a)`` for the kept vertex a, the endpoints of its edge for a midpoint -- the P1
+    prolongation is ``u_fine[i] = (u[parents[i, 0]] + u[parents[i, 1]]) / 2``."""
+    vertices = np.asarray(mesh["vertices"], dtype=np.float64)
+    triangles = np.asarray(mesh["triangles"]).astype(np.int64)
+    edges = np.asarray(mesh["edges"]).astype(np.int64)
+    vertex_markers = np.asarray(mesh["vertex_markers"]).reshape(-1, 1).astype(np.int32)
+    edge_markers = np.asarray(mesh["edge_markers"]).reshape(-1, 1).astype(np.int32)
+    n_v, n_e, n_t = vertices.shape[0], edges.shape[0], triangles.shape[0]
+
+    edge_keys = edges.min(axis=1) * n_v + edges.max(axis=1)
+    by_key = np.argsort(edge_keys, kind="stable")
+    sorted_keys = edge_keys[by_key]
+    if sorted_keys.size > 1 and bool((sorted_keys[1:] == sorted_keys[:-1]).any()):
+        raise ValueError("refine_uniform: the edge list names an edge twice")
+
+    def midpoint(a, b):
+        key = np.minimum(a, b) * n_v + np.maximum(a, b)
+        pos = np.minimum(np.searchsorted(sorted_keys, key), max(n_e - 1, 0))
+        if n_e == 0 or not bool((sorted_keys[pos] == key).all()):
+            raise ValueError("refine_uniform: a triangle side is missing from the edge list")
+        return n_v + by_key[pos]
+
+    t0, t1, t2 = triangles[:, 0], triangles[:, 1], triangles[:, 2]
+    m0, m1, m2 = midpoint(t1, t2), midpoint(t2, t0), midpoint(t0, t1)  # m_k opposite corner k
+    fine_triangles = np.stack(
+        [np.stack(c, axis=1) for c in ((t0, m2, m1), (m2, t1, m0), (m1, m0, t2), (m0, m1, m2))], axis=1
+    ).reshape(4 * n_t, 3)
+
+    mids = n_v + np.arange(n_e, dtype=np.int64)
+    fine_edges = np.concatenate([
+        np.stack([np.stack([edges[:, 0], mids], axis=1), np.stack([mids, edges[:, 1]], axis=1)], axis=1).reshape(-1, 2),
+        np.stack([np.stack(c, axis=1) for c in ((m0, m1), (m1, m2), (m2, m0))], axis=1).reshape(-1, 2),
+    ])
+    fine_edge_markers = np.concatenate([np.repeat(edge_markers, 2, axis=0), np.zeros((3 * n_t, 1), dtype=np.int32)])
+    fine = {
+        "vertices": np.concatenate([vertices, 0.5 * (vertices[edges[:, 0]] + vertices[edges[:, 1]])]),
+        "vertex_markers": np.concatenate([vertex_markers, edge_markers]),
+        "triangles": fine_triangles.astype(np.int32),
+        "edges": fine_edges.astype(np.int32),
+        "edge_markers": fine_edge_markers,
+        "neighbors": _neighbors_from_triangles(fine_triangles, n_v + n_e),
+    }
+    parents = np.concatenate([np.repeat(np.arange(n_v, dtype=np.int64)[:, None], 2, axis=1), edges]).astype(np.int32)
+    order = morton_order(fine["vertices"])
+    fine = permute_mesh(fine, vertex_order=order)
+    return fine, np.ascontiguousarray(parents[order])

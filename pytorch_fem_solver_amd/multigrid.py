@@ -1,0 +1,327 @@
+"""Geometric multigrid for P1 forms: a hierarchy of red refinements of a coarse triangulation, a
+V-cycle on it and conjugate gradients preconditioned by that cycle.
+
+The spaces are nested, so the form re-discretised on a coarser mesh IS the Galerkin operator
+P^T K P of the finer one (for coefficients that the quadrature integrates exactly; otherwise it
+differs by the quadrature error, which a preconditioner does not mind): no sparse triple product.
+Every level has its own ``Basis`` and its own matrix-free operator (``layout="operator"``), the
+transfers are the parent table of ``meshgen.refine_uniform`` and its transpose, and the vector part
+of the cycle runs in three kernels of libtfem_hip (csrc/tfem_mg.hip).
+
+    l = 0:  z[free] = K0[free, free]^-1 r[free], 0 elsewhere          (dense Cholesky, factored once)
+    else:   x = w r;  (nu - 1) x  x += w (r - K x)                    w = omega * m / diag K
+            x += m P vcycle_{l-1}( m_c P^T( m (r - K x) ) )
+            nu x  x += w (r - K x)
+
+with m the 0/1 mask of the level's interior DoFs.  The cycle is a symmetric positive definite
+operator (the post-smoothing is the adjoint of the pre-smoothing), so it may precondition CG.
+"""
+
+from __future__ import annotations
+
+from collections.abc import Mapping
+
+import numpy as np
+import torch
+
+from . import _native, meshgen
+from .basis import Basis, forms
+from .element import ElementTri
+from .mesh import MeshTri
+from .sparse import FormOperator, _into, _is_block
+
+__all__ = ["GeometricMultigrid"]
+
+_MESH_KEYS = ("vertices", "vertex_markers", "triangles", "edges", "edge_markers", "neighbors")
+
+
+def transpose_parents(parents, n_coarse):
+    """(ptr (n_coarse + 1,), idx (2 n_fine,)) int32: row v lists the fine vertices that name the
+    coarse vertex v in ``parents`` (n_fine, 2), ascending; a kept vertex names itself twice and is
+    listed twice.  With the weight 0.5 on every entry this is P^T of the P1 prolongation."""
+    parents = np.asarray(parents)
+    rows = parents.reshape(-1).astype(np.int64)
+    fine = np.repeat(np.arange(parents.shape[0], dtype=np.int64), 2)
+    order = np.argsort(rows, kind="stable")  # `fine` ascends, a stable sort keeps it ascending per row
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n_coarse))])
+    return ptr.astype(np.int32), fine[order].astype(np.int32)
+
+
+class _Level:
+    """What the cycle needs of one mesh of the hierarchy (attributes set by GeometricMultigrid)."""
+
+    def __init__(self, triangulation, basis, op):
+        self.triangulation = triangulation
+        self.basis = basis
+        self.op = op
+        self.engine = basis._engine
+        self.n = int(op.shape[0])
+
+    def __repr__(self):
+        extra = ", renumbered by the engine" if self.engine.renumbered else ""
+        return f"<multigrid level: {self.n} DoFs, {self.op}{extra}>"
+
+
+class GeometricMultigrid:
+    """V(nu, nu)-cycle and multigrid-preconditioned CG for a P1 form on ``levels`` uniform
+    refinements of ``coarse_triangulation`` (a triangle-format dictionary, ``meshgen``).
+
+    ``bilinear`` is the callable of ``Basis.integrate_bilinear_form``; it is traced on every level, so
+    coefficients written as expressions of the integration points are evaluated on every mesh.
+    ``dirichlet=True`` holds the boundary DoFs of every level at zero (``inner_dofs``);
+    ``dirichlet=False`` solves on all DoFs, for forms with a mass term.  ``nu`` damped-Jacobi sweeps
+    with damping ``omega`` before and after the coarse correction.  ``dtype``: the real type of the
+    hierarchy (None: torch's default).  ``element``: the ``ElementTri`` of every level instead of
+    ``ElementTri(1, quadrature_order)``.
+
+    ``basis`` is the finest ``Basis`` (assemble the right-hand side with it), ``operator`` its
+    ``FormOperator``, ``levels`` the list of levels, coarsest first (each with ``basis``, ``op``,
+    ``engine``, ``n``), ``parents`` the parent tables of the refinements (``parents[l - 1]`` takes
+    level l - 1 to level l).
+
+    Refused with NotImplementedError: P2 elements, fracture bases, coefficient data
+    (``basis.coefficient``: its shape belongs to one mesh), a custom set of free DoFs, blocks of
+    right-hand sides; and a coarse mesh with more than ``Basis.DENSE_SOLVE_LIMIT`` free DoFs."""
+
+    def __init__(self, coarse_triangulation, levels, bilinear, quadrature_order=2, dirichlet=True, nu=2,
+                 omega=2.0 / 3.0, dtype=None, *, element=None):
+        from .basis import FractureBasis
+        from .mesh import MeshesTri
+
+        if isinstance(coarse_triangulation, (FractureBasis, MeshesTri)):
+            raise NotImplementedError("GeometricMultigrid: fracture bases (batched meshes) have no hierarchy of "
+                                      "refinements here")
+        if not isinstance(coarse_triangulation, Mapping) or any(k not in coarse_triangulation for k in _MESH_KEYS):
+            raise TypeError("GeometricMultigrid: the coarse mesh is a triangle-format dictionary with the keys "
+                            + ", ".join(_MESH_KEYS))
+        if element is not None and getattr(element, "polynomial_order", 1) != 1:
+            raise NotImplementedError("GeometricMultigrid: P2 elements (the transfers are those of nested P1 spaces)")
+        levels, nu = int(levels), int(nu)
+        if levels < 0 or nu < 1:
+            raise ValueError("GeometricMultigrid: levels >= 0 and nu >= 1")
+        self.nu, self.omega, self.dirichlet = nu, float(omega), bool(dirichlet)
+
+        meshes, self.parents = [{k: np.asarray(coarse_triangulation[k]) for k in _MESH_KEYS}], []
+        for _ in range(levels):
+            fine, parents = meshgen.refine_uniform(meshes[-1])
+            meshes.append(fine)
+            self.parents.append(parents)
+
+        previous = torch.get_default_dtype()
+        if dtype is not None:
+            torch.set_default_dtype(dtype)
+        try:
+            if element is None:  # built here: an element keeps tables in the default dtype of its creation
+                element = ElementTri(polynomial_order=1, integration_order=int(quadrature_order))
+            self.levels = [self._build_level(mesh, element, bilinear) for mesh in meshes]
+        finally:
+            torch.set_default_dtype(previous)
+        self.basis = self.levels[-1].basis
+        self.operator = self.levels[-1].op
+        self.device, self.dtype = self.levels[-1].engine.device, self.levels[-1].engine.dtype
+        self._lib = _native.load()
+        self._real_bytes = torch.empty((), dtype=self.dtype).element_size()
+        with torch.cuda.device(self.device):
+            for l, level in enumerate(self.levels):
+                self._prepare_level(level, None if l == 0 else self.parents[l - 1],
+                                    None if l == 0 else self.levels[l - 1].n)
+            self._factor_coarse(self.levels[0])
+        self._applies = {}  # stream -> the prepared applies of the levels
+
+    # ------------------------------------------------------------------ set-up
+    def _build_level(self, mesh, element, bilinear):
+        basis = Basis(MeshTri(triangulation=mesh), element)
+        engine = basis._engine
+        if engine.n_fractures > 0 or engine.poly_order != 1:
+            raise NotImplementedError("GeometricMultigrid: a P1 basis on one triangulation is needed")
+        try:
+            expr = forms.trace(bilinear, basis, (), {})
+        except ValueError as err:
+            if str(err).startswith("coefficient:"):
+                raise NotImplementedError("GeometricMultigrid: coefficient data (basis.coefficient) has the shape "
+                                          "of ONE mesh; write the coefficient as an expression of the "
+                                          "integration points") from err
+            raise
+        if isinstance(expr, forms.BilinearExpr) and expr.has_coefficients and expr.has_data:
+            raise NotImplementedError("GeometricMultigrid: coefficient data (basis.coefficient) has the shape of ONE "
+                                      "mesh; write the coefficient as an expression of the integration points")
+        op = basis._bilinear_of(expr, "operator")
+        if not isinstance(op, FormOperator):
+            raise TypeError("GeometricMultigrid: the bilinear form did not give an operator")
+        return _Level(mesh, basis, op)
+
+    def _prepare_level(self, level, parents, n_coarse):
+        dev, dtype, n = self.device, self.dtype, level.n
+        diag = level.op.diagonal().to(dev, dtype).reshape(-1)
+        if self.dirichlet:
+            level.free = level.basis._basis_parameters["inner_dofs"].to(dev).reshape(-1).long()
+            level.mask = torch.zeros(n, dtype=dtype, device=dev)
+            level.mask[level.free] = 1
+            w = level.mask / torch.where(diag != 0, diag, torch.ones_like(diag))
+        else:
+            level.free, level.mask = None, None
+            w = 1.0 / diag
+        level.w = (self.omega * w).contiguous()
+        level.x, level.ax, level.r = (torch.zeros(n, dtype=dtype, device=dev) for _ in range(3))
+        if parents is not None:
+            ptr, idx = transpose_parents(parents, n_coarse)
+            level.parents = torch.as_tensor(np.ascontiguousarray(parents, dtype=np.int32), device=dev)
+            level.pt_ptr = torch.as_tensor(ptr, device=dev)
+            level.pt_idx = torch.as_tensor(idx, device=dev)
+
+    def _factor_coarse(self, level):
+        n_free = level.n if level.free is None else int(level.free.numel())
+        if n_free > Basis.DENSE_SOLVE_LIMIT:
+            raise NotImplementedError(f"GeometricMultigrid: the coarse mesh has {n_free} free DoFs, the dense "
+                                      f"coarse solve takes at most {Basis.DENSE_SOLVE_LIMIT}: start from a coarser mesh")
+        dense = level.op.to_csr().to_dense().to(self.device, self.dtype)
+        if level.free is not None:
+            dense = dense[level.free][:, level.free]
+        # K0[free, free]^-1 from the factorisation, once, embedded in the rows and columns of all coarse
+        # DoFs (zero on the held ones): the coarse solve of a cycle is then ONE matrix-vector product
+        # instead of two triangular solves and a gather / scatter (0.35 ms of a 0.6 ms cycle at 900
+        # coarse DoFs, profiles/mg_solve.log)
+        level.inverse = torch.zeros(level.n, level.n, dtype=self.dtype, device=self.device)
+        if n_free > 0:
+            factor, info = torch.linalg.cholesky_ex(dense)
+            if int(info) == 0:
+                inverse = torch.cholesky_inverse(factor)
+            else:
+                # the forms carry the signed determinant: with triangles stored clockwise K0 is not
+                # positive definite, and the factorisation is an LU
+                inverse = torch.linalg.inv(dense)
+            inverse = 0.5 * (inverse + inverse.mT)
+            if level.free is None:
+                level.inverse.copy_(inverse)
+            else:
+                level.inverse[level.free[:, None], level.free[None, :]] = inverse
+
+    def _apply_of(self, level):
+        """``apply(u, out)``: out = K u on the level's buffers, vectors in the caller's numbering."""
+        op, engine = level.op, level.engine
+        if op.matrix_free and not engine.renumbered:
+            return op._rows_into()
+        if not op.matrix_free:
+            csr = op.to_csr().to(self.device)
+            if csr.perm is None:
+                return _into(csr._prepared_spmv)
+
+        def through_matvec(u, out):
+            out.copy_(op.matvec(u))
+
+        return through_matvec
+
+    def _level_applies(self):
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        applies = self._applies.get(key)
+        if applies is None:
+            applies = self._applies[key] = [self._apply_of(level) for level in self.levels]
+        return applies
+
+    # ------------------------------------------------------------------ the cycle
+    def _smooth(self, level, first, stream):
+        status = self._lib.tfem_mg_smooth(_native.ptr(level.x), _native.ptr(level.r),
+                                          None if first else _native.ptr(level.ax), _native.ptr(level.w),
+                                          self._real_bytes, level.n, 1 if first else 0, stream)
+        if status:
+            _native.check(status)
+
+    def _cycle(self, l, applies, stream):
+        level = self.levels[l]
+        if l == 0:
+            torch.mv(level.inverse, level.r, out=level.x)
+            return
+        coarse, apply, lib = self.levels[l - 1], applies[l], self._lib
+        self._smooth(level, True, stream)
+        for _ in range(self.nu - 1):
+            apply(level.x, level.ax)
+            self._smooth(level, False, stream)
+        apply(level.x, level.ax)
+        status = lib.tfem_mg_restrict_residual(
+            _native.ptr(level.pt_ptr), _native.ptr(level.pt_idx), _native.ptr(coarse.mask), _native.ptr(level.mask),
+            _native.ptr(level.r), _native.ptr(level.ax), _native.ptr(coarse.r), self._real_bytes, coarse.n, level.n,
+            stream)
+        if status:
+            _native.check(status)
+        self._cycle(l - 1, applies, stream)
+        status = lib.tfem_mg_prolong_add(_native.ptr(level.parents), _native.ptr(level.mask), _native.ptr(coarse.x),
+                                         _native.ptr(level.x), self._real_bytes, level.n, coarse.n, stream)
+        if status:
+            _native.check(status)
+        for _ in range(self.nu):
+            apply(level.x, level.ax)
+            self._smooth(level, False, stream)
+
+    def _vector(self, v, what):
+        if _is_block(v):
+            raise NotImplementedError(f"GeometricMultigrid.{what}: blocks (N, k) of vectors; one vector (N,) or (N, 1)")
+        flat = v.detach().to(self.device, self.dtype).reshape(-1)
+        if flat.shape[0] != self.levels[-1].n:
+            raise ValueError(f"GeometricMultigrid.{what}: {flat.shape[0]} entries, the finest level has "
+                             f"{self.levels[-1].n} DoFs")
+        return flat
+
+    def _vcycle_into(self, r):
+        """The cycle on the finest level's buffers; returns the buffer that holds the result (valid
+        until the next cycle)."""
+        top = self.levels[-1]
+        top.r.copy_(r)
+        self._cycle(len(self.levels) - 1, self._level_applies(), _native.current_stream(self.device))
+        return top.x
+
+    def vcycle(self, r):
+        """One V-cycle on the residual ``r`` ((N,) or (N, 1), the finest level's DoFs): the
+        approximate solution z of K z = r on the free DoFs, 0 on the held ones; shaped like r."""
+        flat = self._vector(r, "vcycle")
+        with torch.cuda.device(self.device):
+            z = self._vcycle_into(flat).clone()
+        return self.levels[-1].engine._home(z).reshape(r.shape)
+
+    def solve(self, b, x0=None, rtol=1e-10, maxiter=100, free=None):
+        """Conjugate gradients preconditioned by ``vcycle`` for K x = b on the free DoFs (the held
+        ones keep x0's values, 0 by default).  The relative residual |r| / |m b| is checked every
+        iteration.  Returns (x shaped like b, iterations, relative residual)."""
+        if free is not None:
+            raise NotImplementedError("GeometricMultigrid.solve: a custom set of free DoFs; the hierarchy holds the "
+                                      "boundary DoFs of every level (dirichlet=True) or none")
+        top = self.levels[-1]
+        rhs = self._vector(b, "solve")
+        with torch.cuda.device(self.device):
+            apply = self._level_applies()[-1]
+            mask = top.mask
+            x = torch.zeros_like(rhs) if x0 is None else self._vector(x0, "solve").clone()
+            ap = torch.empty_like(rhs)
+            if x0 is None:
+                r = rhs.clone()
+            else:
+                apply(x, ap)
+                r = rhs - ap
+            if mask is not None:
+                r *= mask
+            b_norm = torch.linalg.vector_norm(rhs if mask is None else mask * rhs).clamp_min(
+                torch.finfo(self.dtype).tiny)
+            it, res = 0, float(torch.linalg.vector_norm(r) / b_norm)
+            if res > rtol and maxiter > 0:
+                p = self._vcycle_into(r).clone()
+                rz = torch.dot(r, p)
+                while True:
+                    apply(p, ap)
+                    if mask is not None:
+                        ap *= mask
+                    alpha = rz / torch.dot(p, ap)
+                    x.add_(alpha * p)
+                    r.sub_(alpha * ap)
+                    it += 1
+                    res = float(torch.linalg.vector_norm(r) / b_norm)
+                    if res <= rtol or it >= maxiter:
+                        break
+                    z = self._vcycle_into(r)
+                    rz_new = torch.dot(r, z)
+                    p.mul_(rz_new / rz).add_(z)
+                    rz = rz_new
+        return top.engine._home(x).reshape(b.shape), it, res
+
+    def __repr__(self):
+        sizes = ", ".join(str(level.n) for level in self.levels)
+        return (f"GeometricMultigrid({len(self.levels) - 1} refinements: {sizes} DoFs, V({self.nu},{self.nu}), "
+                f"omega={self.omega:.3g}, dtype={self.dtype})")

@@ -10,6 +10,7 @@ from pytorch_fem_solver_amd import (  # noqa: F401
     ElementTri,
     FractureBasis,
     FracturesTri,
+    GeometricMultigrid,
     InteriorEdgesBasis,
     InteriorEdgesFractureBasis,
     MeshesTri,
@@ -26,4 +27,5 @@ __all__ = [
     "FracturesTri",
     "MeshTri",
     "CoefficientField",
+    "GeometricMultigrid",
 ]
