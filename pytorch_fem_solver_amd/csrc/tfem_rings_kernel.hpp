@@ -814,33 +814,53 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
         for (int i = 0; i < 3; ++i) lamq[i][q] = a.lam[i][q];
       }
     }
+    // The pass's LDS reads first, for all its elements (a lane without an element j holds the zero-filled
+    // code 0: vertex 0 of the tile, a valid address), then the arithmetic across the elements; only the adds
+    // sit behind the lanes' predicate.  With everything of element j behind `l < n_tv` a pass paid one LDS
+    // round trip per element, in series; the operations and their order per element are unchanged.
+    T px[kNE][3], py[kNE][3];
+#pragma unroll
+    for (int j = 0; j < kNE; ++j)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        px[j][i] = vert_at[j][i][0];
+        py[j][i] = vert_at[j][i][1];
+      }
+    T share[kNE][3];  // share[j][i]: to local vertex i of element j
 #pragma unroll
     for (int j = 0; j < kNE; ++j) {
-      const int l = vtid + j * kRingBlock;
-      if (l < d.n_tv) {
-        const unsigned code = codes[j];
-        const T x0 = vert_at[j][0][0], y0 = vert_at[j][0][1], x1 = vert_at[j][1][0], y1 = vert_at[j][1][1],
-                x2 = vert_at[j][2][0], y2 = vert_at[j][2][1];
-        const T det = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0);
-        if constexpr (QL == 4) {
-          // the order-3 rule's structure (RingArgs::qsym): 7 operations instead of 16
-          const T *f4 = fv + j * 4;
-          const T base = src_fma<T>(qs[0], f4[0], qs[1] * ((f4[1] + f4[2]) + f4[3]));
-          add_share(code & 0x3FFu, acc, det * src_fma<T>(qs[2], f4[3], base));
-          add_share((code >> 10) & 0x3FFu, acc, det * src_fma<T>(qs[2], f4[1], base));
-          add_share((code >> 20) & 0x3FFu, acc, det * src_fma<T>(qs[2], f4[2], base));
-        } else {
-          T fw[QL > 0 ? QL : 1];
+      const T det = (px[j][1] - px[j][0]) * (py[j][2] - py[j][0]) - (px[j][2] - px[j][0]) * (py[j][1] - py[j][0]);
+      if constexpr (QL == 4) {
+        // the order-3 rule's structure (RingArgs::qsym): 7 operations instead of 16
+        const T *f4 = fv + j * 4;
+        const T base = src_fma<T>(qs[0], f4[0], qs[1] * ((f4[1] + f4[2]) + f4[3]));
+        share[j][0] = det * src_fma<T>(qs[2], f4[3], base);
+        share[j][1] = det * src_fma<T>(qs[2], f4[1], base);
+        share[j][2] = det * src_fma<T>(qs[2], f4[2], base);
+      } else {
+        T fw[QL > 0 ? QL : 1];
 #pragma unroll
-          for (int q = 0; q < QL; ++q) fw[q] = fv[j * (QL > 0 ? QL : 1) + q] * hwq[q];
+        for (int q = 0; q < QL; ++q) fw[q] = fv[j * (QL > 0 ? QL : 1) + q] * hwq[q];
 #pragma unroll
-          for (int i = 0; i < 3; ++i) {
-            T g = T(0);
+        for (int i = 0; i < 3; ++i) {
+          T g = T(0);
 #pragma unroll
-            for (int q = 0; q < QL; ++q) g = g + fw[q] * lamq[i][q];
-            add_share((code >> (10 * i)) & 0x3FFu, acc, det * g);
-          }
+          for (int q = 0; q < QL; ++q) g = g + fw[q] * lamq[i][q];
+          share[j][i] = det * g;
         }
+      }
+    }
+    // (the empty asm keeps reads and arithmetic where they are written: left alone, hipcc sinks each
+    // element's back behind its predicate)
+#pragma unroll
+    for (int j = 0; j < kNE; ++j)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(share[j][i]));
+#pragma unroll
+    for (int j = 0; j < kNE; ++j) {
+      if (vtid + j * kRingBlock < d.n_tv) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) add_share((codes[j] >> (10 * i)) & 0x3FFu, acc, share[j][i]);
       }
     }
   };

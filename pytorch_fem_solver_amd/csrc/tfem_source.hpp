@@ -104,11 +104,13 @@ constexpr double kSrcInvPi = 0.318309886183790671537767526745;
 constexpr double kSrcTrigFastMax = 1.0e9;
 constexpr double kSrcRoundMagic = 6755399441055744.0;  // 1.5 * 2^52: x + magic rounds x to an integer
 
-// s with its sign flipped when bit 0 of `parity_word` is set
+// s with its sign flipped when bit 0 of `parity_word` is set.  An addition: only bit 31 of the addend
+// can be set and a carry out of bit 31 is dropped, so the sum is the exclusive-or bit for bit -- and
+// shift + add is ONE instruction (v_lshl_add_u32) where shift + xor were two.
 __device__ __forceinline__ double src_flip_sign(double s, unsigned parity_word) {
   typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
   u32x2 b = __builtin_bit_cast(u32x2, s);
-  b.y ^= parity_word << 31;
+  b.y += parity_word << 31;
   return __builtin_bit_cast(double, b);
 }
 
@@ -134,21 +136,25 @@ __device__ __forceinline__ double src_sin_fast_scaled(double x, double c) {
   return src_flip_sign(src_sin_poly_scaled(r, c), src_low_word(kd));
 }
 
+// cos x = (-1)^(k+1) sin(x - (k + 1/2) pi), k = rint(x / pi - 1/2).  The "+1" of the sign rides on the
+// polynomial's odd argument -- the factor (-c) r, or -r without a factor, both operand modifiers -- and
+// not on the parity word (one v_not_b32 per value): products and fused multiply-adds round the same
+// with every sign flipped, and r is never 0 here (k + 1/2 != 0 and pi's low part != 0), so the last
+// step does not cancel to a zero whose sign could differ.
 __device__ __forceinline__ double src_cos_fast_scaled(double x, double c) {
   const double kd = __builtin_fma(x, kSrcInvPi, -0.5) + kSrcRoundMagic;
   const double kh = (kd - kSrcRoundMagic) + 0.5;
   double r = __builtin_fma(-kh, kSrcPiHi, x);
   r = __builtin_fma(-kh, kSrcPiLo, r);
-  return src_flip_sign(src_sin_poly_scaled(r, c), ~src_low_word(kd));
+  return src_flip_sign(src_sin_poly_scaled(r, -c), src_low_word(kd));
 }
 
 __device__ __forceinline__ double src_cos_fast(double x) {
-  // cos x = (-1)^(k+1) sin(x - (k + 1/2) pi), k = rint(x / pi - 1/2)
   const double kd = __builtin_fma(x, kSrcInvPi, -0.5) + kSrcRoundMagic;
   const double kh = (kd - kSrcRoundMagic) + 0.5;
   double r = __builtin_fma(-kh, kSrcPiHi, x);
   r = __builtin_fma(-kh, kSrcPiLo, r);
-  return src_flip_sign(src_sin_poly(r), ~src_low_word(kd));
+  return src_flip_sign(src_sin_poly(-r), src_low_word(kd));
 }
 
 // A library function applied to every entry with ONE inlined copy of it: the loop is not
