@@ -477,6 +477,16 @@ int tfem_p1_rings_source_ops(const void *coords, int real_bytes, int quad_order,
                              const int64_t *plan_layout_host, const tfem_source_program *source,
                              uint8_t *ops_out);
 
+/* What evaluates the program in a tfem_p1_assemble_rings_source / _range launch with these arguments
+ * (those of tfem_p1_rings_source_ops): 0 the general interpreter (one element per pass), 1 the wide
+ * interpreter (programs that hold at most two values, up to four points), 2 straight-line code for a
+ * separable program -- after the proof exactly PUSH_a(c0) F(c1) PUSH_b(c2) G(c3) MUL with {a, b} =
+ * {X, Y} and F, G proven SIN / COS, in an fp64 launch with the 4-point rule.  TFEM_RINGS_SEPARABLE=0 in
+ * the environment keeps such a program on route 1.  The kernel receives the same operation codes on
+ * routes 1 and 2 (tfem_p1_rings_source_ops).  A negative value is minus the status of a refused call. */
+int tfem_p1_rings_source_route(const void *coords, int real_bytes, int quad_order,
+                               const int64_t *plan_layout_host, const tfem_source_program *source);
+
 /* fast_out[i] (HOST, TFEM_SOURCE_MAX_OPS entries) = 1 where operation i of `program` is a SIN or
  * COS whose operand is the PUSH_X / PUSH_Y directly in front of it, with constant c, and
  *   |c| * max_abs_coord * (1 + 1e-9) < 1e9 / 2

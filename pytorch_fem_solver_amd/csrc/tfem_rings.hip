@@ -89,8 +89,9 @@ static void *pick_ring_mass(bool kmat, bool mass, int nq) {
 // nq = 0: matrix only; kmat = false: the load vector alone; src: source program in the launch
 // (those instantiations live in tfem_rings_src.hip)
 template <typename T>
-static void *pick_ring_kernel(int slots, bool mass, bool chunk, int nq, bool src, bool kmat, bool wide) {
-  if (src) return pick_ring_src_kernel<T>(slots, mass, chunk, nq, kmat, wide);
+static void *pick_ring_kernel(int slots, bool mass, bool chunk, int nq, bool src, bool kmat, bool wide,
+                              bool separable) {
+  if (src) return pick_ring_src_kernel<T>(slots, mass, chunk, nq, kmat, wide, separable);
   if (slots == 7)
     return chunk ? pick_ring_mass<T, 7, true>(kmat, mass, nq) : pick_ring_mass<T, 7, false>(kmat, mass, nq);
   return chunk ? pick_ring_mass<T, 15, true>(kmat, mass, nq) : pick_ring_mass<T, 15, false>(kmat, mass, nq);
@@ -107,15 +108,34 @@ static bool ring_src_wide(const tfem_source_program *source) {
 // (tfem_ring_plan_vouch_coords: layout[29] the array it vouched for, layout[31] the bound) the fp64
 // launches of the wide interpreter -- the one that knows the proven operations -- skip the range tests
 // of the SIN / COS the host proves; everything else is converted as it is.
-template <typename T>
-static int ring_src_convert(const int64_t *z, const void *coords, int nq, const tfem_source_program *source,
-                            SrcProgram<T> *out) {
+// (-1: the caller vouched for nothing, or for another array)
+static double ring_coord_bound(const int64_t *z, const void *coords) {
   double coord_bound = -1.0;
   if (z[29] != 0 && uintptr_t(z[29]) == reinterpret_cast<uintptr_t>(coords))
     std::memcpy(&coord_bound, &z[31], sizeof(coord_bound));
+  return coord_bound;
+}
+
+template <typename T>
+static int ring_src_convert(const int64_t *z, const void *coords, int nq, const tfem_source_program *source,
+                            SrcProgram<T> *out) {
+  const double coord_bound = ring_coord_bound(z, coords);
   if (sizeof(T) == 8 && coord_bound >= 0.0 && ring_src_runs_wide(nq, ring_src_wide(source)))
     return src_convert_proven<T>(source, coord_bound, out);
   return src_convert<T>(source, out);
+}
+
+// What evaluates the program in the launch: 0 the general interpreter, 1 the wide one, 2 straight-line
+// code for a separable program (src_is_separable: fp64, four points, every sine / cosine proven for
+// THIS coordinate array).  TFEM_RINGS_SEPARABLE=0 keeps such a program on the interpreter.
+template <typename T>
+static int ring_src_route(const int64_t *z, const void *coords, int nq, const tfem_source_program *source) {
+  if (!ring_src_runs_wide(nq, ring_src_wide(source))) return 0;
+  bool separable = sizeof(T) == 8 && nq == 4;
+  if (const char *v = std::getenv("TFEM_RINGS_SEPARABLE")) separable = separable && std::atoi(v) != 0;
+  if (!separable) return 1;
+  const double coord_bound = ring_coord_bound(z, coords);
+  return coord_bound >= 0.0 && src_is_separable(source, coord_bound) ? 2 : 1;
 }
 
 template <typename T>
@@ -256,7 +276,8 @@ static int launch_rings(const RingLaunch &L) {
   if (const char *v = std::getenv("TFEM_RINGS_STORES")) a.plain_stores = std::strcmp(v, "plain") == 0;
   // programs that never hold more than two values: three elements per pass of the interpreter
   const bool wide = src && ring_src_wide(L.source);
-  void *kernel = pick_ring_kernel<T>(slots, mass, chunk, load ? tables.nq : 0, src, kmat, wide);
+  const bool separable = src && ring_src_route<T>(z, L.coords, tables.nq, L.source) == 2;
+  void *kernel = pick_ring_kernel<T>(slots, mass, chunk, load ? tables.nq : 0, src, kmat, wide, separable);
   if (!kernel) return fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
   // resident workgroups: what LDS and registers allow per CU, on every CU
   int per_cu = 0;
@@ -329,6 +350,20 @@ int tfem_p1_rings_source_ops(const void *coords, int real_bytes, int quad_order,
     return fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
   return real_bytes == 8 ? ring_src_ops<double>(plan_layout_host, coords, tables.nq, source, ops_out)
                          : ring_src_ops<float>(plan_layout_host, coords, tables.nq, source, ops_out);
+}
+
+int tfem_p1_rings_source_route(const void *coords, int real_bytes, int quad_order, const int64_t *plan_layout_host,
+                               const tfem_source_program *source) {
+  using namespace tfem;
+  if (real_bytes != 4 && real_bytes != 8) return -fail(TFEM_ERR_INVALID_ARGUMENT, "real_bytes must be 4 or 8");
+  if (!plan_layout_host || !source) return -fail(TFEM_ERR_INVALID_ARGUMENT, "NULL pointer");
+  TriTables tables;
+  if (!build_tri_tables(quad_order, real_bytes, &tables))
+    return -fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
+  const int st = src_validate(source);
+  if (st != TFEM_OK) return -st;
+  return real_bytes == 8 ? ring_src_route<double>(plan_layout_host, coords, tables.nq, source)
+                         : ring_src_route<float>(plan_layout_host, coords, tables.nq, source);
 }
 
 int tfem_ring_capacity(int what) {

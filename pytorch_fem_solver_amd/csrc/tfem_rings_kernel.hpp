@@ -566,9 +566,11 @@ __device__ __forceinline__ void ring_load_fq(ring_rsrc_t r, unsigned byte, T (&v
 // coordinates the tile holds in LDS anyway, f is evaluated there (tfem_source.hpp) and reduced
 // to g[T][.] as above.  That happens at the START of the tile's iteration (its coordinates are
 // complete after the previous iteration's barrier), behind the issue of the next tile's loads.
-// The sixth parameter is read nowhere and always false: it keeps KMAT and SRC at positions 6 and 7
-// of the demangled kernel name, where bench.py finds the bench launches in the committed profiles.
-template <typename T, int SLOTS, bool MASS, bool CHUNK, int QL, bool, bool KMAT = true, int SRC = 0>
+// SEP (the sixth parameter, with KMAT and SRC behind it at positions 6 and 7 of the demangled kernel
+// name, where bench.py finds the bench launches in the committed profiles): the program is a separable
+// one, k U(a x) V(b y) with proven sines / cosines (host: src_is_separable), and phase G evaluates it in
+// straight-line code -- no interpreter in the kernel (fp64, Q = 4, SRC = 2 only).
+template <typename T, int SLOTS, bool MASS, bool CHUNK, int QL, bool SEP, bool KMAT = true, int SRC = 0>
 // The matrix-only 15-slot instantiations are asked for 3 waves per SIMD: left alone, hipcc's
 // scheduler hoists every LDS read of the unrolled fan loop and ends at 250 VGPRs (2 waves); with
 // the bound it needs 112-128 and nothing spills (the load-vector instantiations would spill).
@@ -582,6 +584,7 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   constexpr bool kCoordsToLds = SRC == 2 && sizeof(T) == 8;
   static_assert(KMAT || LOAD, "nothing to assemble");
   static_assert(LOAD || !SRC, "a source program needs a load vector");
+  static_assert(!SEP || (SRC == 2 && QL == 4 && sizeof(T) == 8), "the separable form: fp64, four points, wide passes");
   constexpr int kEW = (12 * SLOTS + 31) / 32;  // dwords of packed 12-bit slot codes per row: 3 or 6
   extern __shared__ __attribute__((aligned(16))) unsigned char ring_smem[];
   T *xy = reinterpret_cast<T *>(ring_smem);                      // [2][2 * lds_vert]
@@ -639,11 +642,12 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
       return __builtin_amdgcn_readfirstlane((j < per && t < a.n_tiles) ? t : -1);
     }
   };
-  const ring_rsrc_t r_coords = ring_rsrc(a.coords, a.coords_bytes);
-  const ring_rsrc_t r_plan = ring_rsrc(a.plan, a.plan_bytes);
-  const ring_rsrc_t r_vals = ring_rsrc(a.vals, a.vals_bytes);
+  // (not const: the SEP instantiations form them anew behind every phase G)
+  ring_rsrc_t r_coords = ring_rsrc(a.coords, a.coords_bytes);
+  ring_rsrc_t r_plan = ring_rsrc(a.plan, a.plan_bytes);
+  ring_rsrc_t r_vals = ring_rsrc(a.vals, a.vals_bytes);
   const ring_rsrc_t r_fq = ring_rsrc(a.fq, a.fq_bytes);
-  const ring_rsrc_t r_fout = ring_rsrc(a.fout, a.fout_bytes);
+  ring_rsrc_t r_fout = ring_rsrc(a.fout, a.fout_bytes);
   constexpr unsigned kRecBytes = unsigned(4 * RingRec<SLOTS>::kWords);
   constexpr unsigned kNone = 0x3FFFFFFu;  // row / vertex index behind every array: loads give 0
   if (FQ && tid < 4)  // the spare entries slots without a triangle read (times a zero determinant)
@@ -662,8 +666,11 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     for (int i = tid; i < 3 * acc_stride; i += kRingBlock) accs[i] = T(0);
 
   // SRC: the program, one operation per lane, for the whole launch
+  // (SEP: no lanes, what the passes need of the program are its first four constants and three bits)
   SrcLanes<T> prog;
-  if constexpr (SRC) prog = src_load_lanes<T>(src_in_kernarg<T>(__builtin_offsetof(RingArgs<T>, src)));
+  if constexpr (SRC && !SEP) prog = src_load_lanes<T>(src_in_kernarg<T>(__builtin_offsetof(RingArgs<T>, src)));
+  int sep_flags = 0;
+  if constexpr (SEP) sep_flags = src_separable_flags<T>(src_in_kernarg<T>(__builtin_offsetof(RingArgs<T>, src)));
   RingRec<SLOTS> rec, rec_ld;
   uint32_t se[FQ ? kEW : 1], se_ld[FQ ? kEW : 1];  // slot codes of the row (load vector from fq)
   unsigned eid[FQ ? kRingElemPerLane : 1], eid_ld[FQ ? kRingElemPerLane : 1];  // element ids, like gid_*
@@ -783,7 +790,23 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     for (int j = 0; j < kNE; ++j)
 #pragma unroll
       for (int i = 0; i < 3; ++i) vert_at[j][i] = xyc + 2 * __builtin_amdgcn_ubfe(codes[j], 10 * i, 10);
-    src_run_wide<T, (QL > 0 ? QL : 1), kNE>(prog, vert_at, a.lam, __builtin_offsetof(RingArgs<T>, lam), fv);
+    // SEP: ONE batch of LDS reads per pass -- the six coordinates of every element serve both factors'
+    // points and, further down, the determinants (the interpreter fetches them per coordinate push and
+    // cannot keep them: two stack entries are live while arbitrary operations run)
+    T px[kNE][3], py[kNE][3];
+    if constexpr (SEP) {
+#pragma unroll
+      for (int j = 0; j < kNE; ++j)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          px[j][i] = vert_at[j][i][0];
+          py[j][i] = vert_at[j][i][1];
+        }
+      src_separable<T, kNE>(sep_flags, __builtin_offsetof(RingArgs<T>, src) + __builtin_offsetof(SrcProgram<T>, c),
+                            __builtin_offsetof(RingArgs<T>, lam), px, py, fv);
+    } else {
+      src_run_wide<T, (QL > 0 ? QL : 1), kNE>(prog, vert_at, a.lam, __builtin_offsetof(RingArgs<T>, lam), fv);
+    }
     // the constants of the shares; fp64: scalar loads in flight during the determinants' LDS reads
     // (src_kernarg_table: not carried through the interpreter in spill lanes)
     constexpr int kQ = QL > 0 ? QL : 1;
@@ -818,14 +841,15 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     // code 0: vertex 0 of the tile, a valid address), then the arithmetic across the elements; only the adds
     // sit behind the lanes' predicate.  With everything of element j behind `l < n_tv` a pass paid one LDS
     // round trip per element, in series; the operations and their order per element are unchanged.
-    T px[kNE][3], py[kNE][3];
+    if constexpr (!SEP) {
 #pragma unroll
-    for (int j = 0; j < kNE; ++j)
+      for (int j = 0; j < kNE; ++j)
 #pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        px[j][i] = vert_at[j][i][0];
-        py[j][i] = vert_at[j][i][1];
-      }
+        for (int i = 0; i < 3; ++i) {
+          px[j][i] = vert_at[j][i][0];
+          py[j][i] = vert_at[j][i][1];
+        }
+    }
     T share[kNE][3];  // share[j][i]: to local vertex i of element j
 #pragma unroll
     for (int j = 0; j < kNE; ++j) {
@@ -1048,8 +1072,22 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
       // ---- G ---- source values of tile k (its coordinates are complete).  Before A: the
       // registers of tile k+1's loads are not live while the program runs (3 workgroups per CU)
       compute_g(dc, tev, xy + cur * 2 * a.lds_vert, accs + a_cur * acc_stride, k);
-      // (the barrier behind G stands in front of the rows' read of their sums: the next tile's
-      // loads and the rows' own arithmetic need nothing of G)
+      if constexpr (SEP) {
+        // The buffer descriptors are read again from the kernel-argument segment instead of being carried
+        // through G: the straight-line pass needs the scalar registers, and what it pushed out came back
+        // either from spill lanes (a v_readlane each) or by hipcc re-loading the by-value argument, which
+        // left the kernel a private segment of 36 bytes that no instruction touches.  The opaque pointer
+        // keeps the loads here (src_kernarg_table); nothing in front of G but the coordinate loads, which
+        // take last iteration's r_coords, uses a descriptor.
+        typedef const RingArgs<T> __attribute__((address_space(4))) *ring_kernargs;
+        const ring_kernargs ka = (ring_kernargs)src_kernarg_table<char>(0);
+        r_coords = ring_rsrc(ka->coords, ka->coords_bytes);
+        r_plan = ring_rsrc(ka->plan, ka->plan_bytes);
+        r_vals = ring_rsrc(ka->vals, ka->vals_bytes);
+        r_fout = ring_rsrc(ka->fout, ka->fout_bytes);
+      }
+      // (the barrier behind G stands in front of the rows' read of their sums -- SEP: behind D --: the
+      // next tile's loads and the rows' own arithmetic need nothing of G)
     }
     // ---- A ----
     phase_a();
@@ -1084,7 +1122,7 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
       }
     }
     T facc = T(0);
-    if (SRC) {  // the row's sum is complete behind the barrier: one LDS read
+    if (SRC && !SEP) {  // the row's sum is complete behind the barrier: one LDS read
       ring_lds_barrier();
       const unsigned from = (hin & 0xFFFFu) == 0xFFFFu ? unsigned(a.lds_vert) : (hin & 0xFFFFu);  // lds_vert: the zero
       facc = accs[a_cur * acc_stride + (my_row < dc.row1 ? my_row : a.lds_vert)] + accs[a_prev * acc_stride + from];
@@ -1139,6 +1177,22 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
         ring_store<T, SLOTS>(my_stage, total, pre, rowstart, len_c, r_vals, a.plain_stores);
       }
     }
+    if (SEP) {
+      // SEP: the barrier behind G stands HERE, behind C and D.  The waves of a tile run two or three rounds
+      // of G, and those with two waited at it for the one with three before they did anything of C and D --
+      // none of which needs G's sums.  Hazards of what moved in front of it: the zeroing writes the buffer
+      // a_next, whose last readers were the rows of the previous tile, in front of ITS barrier E; xy[cur ^ 1]
+      // is written by the coordinate loads issued at the top of the iteration either way (`park` copies
+      // nothing in these launches), last read by phases G and B of the previous iteration, in front of that
+      // same barrier, while the waves still in G read xy[cur]; the stage is wave-private.  C's vmcnt(0)
+      // stays ahead of the K stores, so it waits for loads issued a row phase ago and for the stores of the
+      // previous tile only.  (Moved in every SRC instantiation it gave the other programs nothing and cost
+      // the general interpreter's depth-3 program 1 %, profiles/fused_separable.log: they keep the barrier
+      // in front of C.)
+      ring_lds_barrier();
+      const unsigned from = (hin & 0xFFFFu) == 0xFFFFu ? unsigned(a.lds_vert) : (hin & 0xFFFFu);
+      facc = accs[a_cur * acc_stride + (my_row < dc.row1 ? my_row : a.lds_vert)] + accs[a_prev * acc_stride + from];
+    }
     if (LOAD && dc.row0 + lane < dc.row1) {
       const unsigned byte = gid_row * unsigned(sizeof(T));
       if constexpr (sizeof(T) == 8)
@@ -1179,8 +1233,9 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
 
 // SRC instantiations (tfem_rings_src.hip): nq > 0; kmat = false: the load vector alone.
 // wide: the three-elements-per-pass interpreter (programs of depth <= 2)
+// separable: the straight-line instantiations (ring_src_route's 2; fp64, nq = 4, wide)
 template <typename T>
-void *pick_ring_src_kernel(int slots, bool mass, bool chunk, int nq, bool kmat, bool wide);
+void *pick_ring_src_kernel(int slots, bool mass, bool chunk, int nq, bool kmat, bool wide, bool separable);
 // Which interpreter pick_ring_src_kernel's launch runs (`wide`: the program's depth allows the wide
 // one): with Q = 6 the wide interpreter would hold 2 x 18 doubles, so it keeps the one-element form.
 // The proven sin / cos operations (src_convert_proven) are known to the wide interpreter only.

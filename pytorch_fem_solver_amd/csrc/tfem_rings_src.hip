@@ -45,13 +45,30 @@ static void *pick_src_slots(int slots, bool mass, bool chunk, int nq, bool kmat)
   return chunk ? pick_src_mass<T, 15, true, SRC>(kmat, mass, nq) : pick_src_mass<T, 15, false, SRC>(kmat, mass, nq);
 }
 
+// The separable straight-line instantiations (tfem_rings_kernel.hpp, SEP): fp64, four points, wide passes.
+template <int SLOTS, bool CHUNK>
+static void *pick_separable_mass(bool kmat, bool mass) {
+  if (!kmat) return reinterpret_cast<void *>(k_p1_rings<double, SLOTS, false, CHUNK, 4, true, false, 2>);
+  return mass ? reinterpret_cast<void *>(k_p1_rings<double, SLOTS, true, CHUNK, 4, true, true, 2>)
+              : reinterpret_cast<void *>(k_p1_rings<double, SLOTS, false, CHUNK, 4, true, true, 2>);
+}
+
+static void *pick_separable(int slots, bool mass, bool chunk, bool kmat) {
+  if (slots == 7) return chunk ? pick_separable_mass<7, true>(kmat, mass) : pick_separable_mass<7, false>(kmat, mass);
+  return chunk ? pick_separable_mass<15, true>(kmat, mass) : pick_separable_mass<15, false>(kmat, mass);
+}
+
 template <typename T>
-void *pick_ring_src_kernel(int slots, bool mass, bool chunk, int nq, bool kmat, bool wide) {
+void *pick_ring_src_kernel(int slots, bool mass, bool chunk, int nq, bool kmat, bool wide, bool separable) {
+  if (separable) {  // the caller's recogniser guarantees the rest; anything else is its error
+    if (sizeof(T) != 8 || nq != 4 || !ring_src_runs_wide(nq, wide)) return nullptr;
+    return pick_separable(slots, mass, chunk, kmat);
+  }
   if (ring_src_runs_wide(nq, wide)) return pick_src_slots<T, 2>(slots, mass, chunk, nq, kmat);
   return pick_src_slots<T, 1>(slots, mass, chunk, nq, kmat);
 }
 
-template void *pick_ring_src_kernel<double>(int, bool, bool, int, bool, bool);
-template void *pick_ring_src_kernel<float>(int, bool, bool, int, bool, bool);
+template void *pick_ring_src_kernel<double>(int, bool, bool, int, bool, bool, bool);
+template void *pick_ring_src_kernel<float>(int, bool, bool, int, bool, bool, bool);
 
 }  // namespace tfem

@@ -108,6 +108,17 @@ int src_convert_proven(const tfem_source_program *in, double coord_bound, SrcPro
 template int src_convert_proven<double>(const tfem_source_program *, double, SrcProgram<double> *);
 template int src_convert_proven<float>(const tfem_source_program *, double, SrcProgram<float> *);
 
+bool src_is_separable(const tfem_source_program *in, double coord_bound) {
+  if (!in || in->n_ops != 5 || src_validate(in) != TFEM_OK) return false;
+  const int a = in->ops[0], b = in->ops[2];
+  if (!((a == TFEM_SRC_PUSH_X && b == TFEM_SRC_PUSH_Y) || (a == TFEM_SRC_PUSH_Y && b == TFEM_SRC_PUSH_X))) return false;
+  for (int i = 1; i <= 3; i += 2)
+    if (in->ops[i] != TFEM_SRC_SIN && in->ops[i] != TFEM_SRC_COS) return false;
+  if (in->ops[4] != TFEM_SRC_MUL) return false;
+  uint8_t fast[kSrcMaxOps];
+  return src_trig_proof(in, coord_bound, fast) == 2 && fast[1] && fast[3];
+}
+
 namespace {
 
 constexpr int kSrcBlock = 256;

@@ -51,6 +51,11 @@ int src_trig_proof(const tfem_source_program *in, double coord_bound, uint8_t (&
 // src_convert with the proven SIN / COS replaced (T = double; float launches take sinf / cosf anyway)
 template <typename T>
 int src_convert_proven(const tfem_source_program *in, double coord_bound, SrcProgram<T> *out);
+// The separable form k U(a x) V(b y): true when the program is, after the proof at `coord_bound`, exactly
+//   PUSH_a(c0) F(c1) PUSH_b(c2) G(c3) MUL,  {a, b} = {X, Y},  F, G proven SIN / COS
+// (the manufactured-solution sources sin sin, sin cos, cos cos).  The fp64 launches with four points
+// evaluate such a program without the interpreter (src_separable).
+bool src_is_separable(const tfem_source_program *in, double coord_bound);
 
 #if defined(__HIPCC__)
 
@@ -543,6 +548,73 @@ __device__ __forceinline__ void src_run_wide(const SrcLanes<T> &prog, const T *c
 #undef TFEM_SRC_SET
 #pragma unroll
   for (int i = 0; i < N; ++i) out[i] = s0[i];
+}
+
+// Separable programs (host: src_is_separable), fp64 launches with four points: c1 F(c0 a) * c3 G(c2 b)
+// written out -- no decode, no stack, and the coordinates come from the caller's registers, who read all
+// six of an element's once for both factors and the determinant.  The arithmetic is src_run_wide's,
+// operation for operation: the points as c * fma(l2, v2, fma(l1, v1, l0 * v0)) (see the note at its
+// coordinate pushes), the proven functions with their factor folded in, then the product.  A product
+// rounds the same in either operand order, so which coordinate the program pushes first only decides
+// where its constants sit.
+// What the kernel keeps of the program (one scalar register for the whole launch):
+constexpr int kSepYFirst = 1, kSepXCos = 2, kSepYCos = 4;
+
+template <typename T>
+__device__ __forceinline__ int src_separable_flags(src_const_ptr<T> p) {
+  const uint32_t w = p->opw[0];  // operations 0 .. 3
+  const bool y_first = (w & 0xFFu) == uint32_t(TFEM_SRC_PUSH_Y);
+  const uint32_t f_first = (w >> 8) & 0xFFu, f_second = w >> 24;
+  const uint32_t fx = y_first ? f_second : f_first, fy = y_first ? f_first : f_second;
+  return (y_first ? kSepYFirst : 0) | (fx == uint32_t(kSrcCosProven) ? kSepXCos : 0) |
+         (fy == uint32_t(kSrcCosProven) ? kSepYCos : 0);
+}
+
+// `c_offset`, `lam_offset`: where SrcProgram::c and the table l_i(q) sit in the kernel-argument segment.
+// Each factor reads its two constants and the table there when it starts (scalar loads, src_kernarg_table):
+// carried through the other factor's polynomials they would sit in spill lanes.  The branches are
+// wave-uniform.
+template <typename T, int NE>
+__device__ __forceinline__ void src_separable(int flags, size_t c_offset, size_t lam_offset, const T (&px)[NE][3],
+                                              const T (&py)[NE][3], T (&out)[NE * 4]) {
+  static_assert(sizeof(T) == 8, "fp64 launches only");
+  constexpr int QL = 4, N = NE * QL;
+  const src_const_tab<T> ct = src_kernarg_table<T>(c_offset);
+  const int ix = (flags & kSepYFirst) ? 2 : 0;
+  const T cx = ct[ix], cfx = ct[ix + 1];
+#define TFEM_SRC_SEP_POINTS(dst, v, c)                                                             \
+  {                                                                                                \
+    const src_const_tab<T> ltab = src_kernarg_table<T>(lam_offset);                                \
+    T lam[3][QL];                                                                                  \
+    _Pragma("unroll") for (int k = 0; k < 3; ++k)                                                  \
+      _Pragma("unroll") for (int q = 0; q < QL; ++q) lam[k][q] = ltab[k * kMaxQuad + q];           \
+    _Pragma("unroll") for (int e = 0; e < NE; ++e)                                                 \
+      _Pragma("unroll") for (int q = 0; q < QL; ++q)                                               \
+        dst[e * QL + q] =                                                                          \
+            c * src_fma<T>(lam[2][q], v[e][2], src_fma<T>(lam[1][q], v[e][1], lam[0][q] * v[e][0])); \
+  }
+  TFEM_SRC_SEP_POINTS(out, px, cx)
+  if (flags & kSepXCos) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = src_cos_fast_scaled(out[i], cfx);
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = src_sin_fast_scaled(out[i], cfx);
+  }
+  T g[N];
+  const src_const_tab<T> ct2 = src_kernarg_table<T>(c_offset);  // (a second opaque pointer: loaded here, not carried)
+  const T cy = ct2[2 - ix], cfy = ct2[3 - ix];
+  TFEM_SRC_SEP_POINTS(g, py, cy)
+#undef TFEM_SRC_SEP_POINTS
+  if (flags & kSepYCos) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) g[i] = src_cos_fast_scaled(g[i], cfy);
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) g[i] = src_sin_fast_scaled(g[i], cfy);
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) out[i] = out[i] * g[i];
 }
 
 #endif  // __HIPCC__

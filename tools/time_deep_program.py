@@ -1,5 +1,5 @@
 import math, os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import pytorch_fem_solver_amd as tf
 from pytorch_fem_solver_amd import meshgen
 from pytorch_fem_solver_amd.basis import forms
