@@ -487,6 +487,17 @@ int tfem_p1_rings_source_ops(const void *coords, int real_bytes, int quad_order,
 int tfem_p1_rings_source_route(const void *coords, int real_bytes, int quad_order,
                                const int64_t *plan_layout_host, const tfem_source_program *source);
 
+/* The three constants an fp64 launch with the 4-point rule multiplies the source values with when it forms
+ * an element's shares g_i = W0 f_0 + W1 (f_1 + f_2 + f_3) + W2 f_q(i) -> weights_out[0..2] (HOST); zeros
+ * for float32 and the other rules.  On routes 0 and 1 they are the rule's own (c0 w_0 / 2, b w_1 / 2,
+ * d w_1 / 2); on route 2 the kernel evaluates the two bare functions and the factors c1, c3 behind them
+ * ride on the constants as k = c1 c3, whichever coordinate the program pushes first.  A program whose k is
+ * not finite, or is subnormal while c1 and c3 are not, is not taken on route 2.  Returns the route
+ * (tfem_p1_rings_source_route) or minus the status of a refused call.  For tests and tools. */
+int tfem_p1_rings_source_weights(const void *coords, int real_bytes, int quad_order,
+                                 const int64_t *plan_layout_host, const tfem_source_program *source,
+                                 double *weights_out);
+
 /* fast_out[i] (HOST, TFEM_SOURCE_MAX_OPS entries) = 1 where operation i of `program` is a SIN or
  * COS whose operand is the PUSH_X / PUSH_Y directly in front of it, with constant c, and
  *   |c| * max_abs_coord * (1 + 1e-9) < 1e9 / 2

@@ -218,6 +218,7 @@ SIGNATURES = {
     "tfem_ring_plan_vouch_coords": (c_int, [c_void_p, c_void_p, c_double]),
     "tfem_p1_rings_source_ops": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tfem_p1_rings_source_route": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "tfem_p1_rings_source_weights": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tfem_source_eval": (
         c_int,
         [c_void_p, c_int, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p],

@@ -138,6 +138,39 @@ static int ring_src_route(const int64_t *z, const void *coords, int nq, const tf
   return coord_bound >= 0.0 && src_is_separable(source, coord_bound) ? 2 : 1;
 }
 
+// The structure of the 4-point rule the QL = 4 instantiations use (RingArgs::qsym); false: the rule in
+// `tables` is not the reference's order-3 rule.
+// (c0, a, b from the rule's literals; 1 - xi - eta of the reference's table is the same to an ulp)
+template <typename T>
+static bool ring_rule_structure(const TriTables &tables, T (&qsym)[6]) {
+  const double c0 = tables.lam[0][1], aa = tables.lam[1][1], b = tables.lam[1][2], d = aa - b;
+  const int at[4] = {0, 1, 2, 0};
+  const double tol = sizeof(T) == 8 ? 1e-15 : 1e-6;  // the tables are rounded to the launch's real type
+  auto near = [tol](double x, double y) { return std::fabs(x - y) <= tol; };
+  bool ok = tables.hw[1] == tables.hw[2] && tables.hw[1] == tables.hw[3];
+  for (int i = 0; i < 3; ++i) {
+    ok = ok && near(tables.lam[0][i], c0);
+    for (int q = 1; q < 4; ++q) ok = ok && near(tables.lam[q][i], i == at[q] ? aa : b);
+  }
+  if (!ok) return false;
+  qsym[0] = T(c0);
+  qsym[1] = T(b);
+  qsym[2] = T(d);
+  qsym[3] = T(c0) * T(tables.hw[0]);
+  qsym[4] = T(b) * T(tables.hw[1]);
+  qsym[5] = T(d) * T(tables.hw[1]);
+  return true;
+}
+
+// The share constants of a launch on route 2: qsym[3..5] with k = c1 c3, the product of the factors behind
+// the program's two functions, on them (RingArgs::qsym).  Which coordinate the program pushes first does
+// not enter: the product is the same either way.
+template <typename T>
+static void ring_separable_weights(const tfem_source_program *source, T (&qsym)[6]) {
+  const T k = src_separable_factor<T>(source);
+  for (int i = 3; i < 6; ++i) qsym[i] = k * qsym[i];
+}
+
 template <typename T>
 static int ring_src_ops(const int64_t *z, const void *coords, int nq, const tfem_source_program *source,
                         uint8_t *ops_out) {
@@ -200,26 +233,8 @@ static int launch_rings(const RingLaunch &L) {
       a.lam[i][q] = T(tables.lam[q][i]);
       a.hw[q] = T(tables.hw[q]);
     }
-  if (src && tables.nq == 4) {
-    // the structure of the 4-point rule the QL = 4 instantiations use (RingArgs::qsym)
-    // (c0, a, b from the rule's literals; 1 - xi - eta of the reference's table is the same to an ulp)
-    const double c0 = tables.lam[0][1], aa = tables.lam[1][1], b = tables.lam[1][2], d = aa - b;
-    const int at[4] = {0, 1, 2, 0};
-    const double tol = sizeof(T) == 8 ? 1e-15 : 1e-6;  // the tables are rounded to the launch's real type
-    auto near = [tol](double x, double y) { return std::fabs(x - y) <= tol; };
-    bool ok = tables.hw[1] == tables.hw[2] && tables.hw[1] == tables.hw[3];
-    for (int i = 0; i < 3; ++i) {
-      ok = ok && near(tables.lam[0][i], c0);
-      for (int q = 1; q < 4; ++q) ok = ok && near(tables.lam[q][i], i == at[q] ? aa : b);
-    }
-    if (!ok) return fail(TFEM_ERR_UNSUPPORTED, "the 4-point rule is not the reference's order-3 rule");
-    a.qsym[0] = T(c0);
-    a.qsym[1] = T(b);
-    a.qsym[2] = T(d);
-    a.qsym[3] = T(c0) * T(tables.hw[0]);
-    a.qsym[4] = T(b) * T(tables.hw[1]);
-    a.qsym[5] = T(d) * T(tables.hw[1]);
-  }
+  if (src && tables.nq == 4 && !ring_rule_structure<T>(tables, a.qsym))
+    return fail(TFEM_ERR_UNSUPPORTED, "the 4-point rule is not the reference's order-3 rule");
   if (src) {
     if (z[20] == 0 || z[21] == 0)
       return fail(TFEM_ERR_UNSUPPORTED, "the ring plan carries no element vertex table (source programs)");
@@ -277,6 +292,7 @@ static int launch_rings(const RingLaunch &L) {
   // programs that never hold more than two values: three elements per pass of the interpreter
   const bool wide = src && ring_src_wide(L.source);
   const bool separable = src && ring_src_route<T>(z, L.coords, tables.nq, L.source) == 2;
+  if (separable) ring_separable_weights<T>(L.source, a.qsym);  // (route 2: the 4-point rule, qsym is filled)
   void *kernel = pick_ring_kernel<T>(slots, mass, chunk, load ? tables.nq : 0, src, kmat, wide, separable);
   if (!kernel) return fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
   // resident workgroups: what LDS and registers allow per CU, on every CU
@@ -364,6 +380,25 @@ int tfem_p1_rings_source_route(const void *coords, int real_bytes, int quad_orde
   if (st != TFEM_OK) return -st;
   return real_bytes == 8 ? ring_src_route<double>(plan_layout_host, coords, tables.nq, source)
                          : ring_src_route<float>(plan_layout_host, coords, tables.nq, source);
+}
+
+int tfem_p1_rings_source_weights(const void *coords, int real_bytes, int quad_order, const int64_t *plan_layout_host,
+                                 const tfem_source_program *source, double *weights_out) {
+  using namespace tfem;
+  if (!weights_out) return -fail(TFEM_ERR_INVALID_ARGUMENT, "NULL pointer");
+  const int route = tfem_p1_rings_source_route(coords, real_bytes, quad_order, plan_layout_host, source);
+  if (route < 0) return route;
+  TriTables tables;
+  if (!build_tri_tables(quad_order, real_bytes, &tables))
+    return -fail(TFEM_ERR_UNSUPPORTED, "Integration order not implemented");
+  double qsym[6] = {};
+  if (tables.nq == 4 && real_bytes == 8) {
+    if (!ring_rule_structure<double>(tables, qsym))
+      return -fail(TFEM_ERR_UNSUPPORTED, "the 4-point rule is not the reference's order-3 rule");
+    if (route == 2) ring_separable_weights<double>(source, qsym);
+  }
+  for (int i = 0; i < 3; ++i) weights_out[i] = qsym[3 + i];
+  return route;
 }
 
 int tfem_ring_capacity(int what) {

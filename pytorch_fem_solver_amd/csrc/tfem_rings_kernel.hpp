@@ -51,6 +51,9 @@ struct RingArgs {
   // points with weights (b, b, b) + d on vertex 1, 2, 0; element_tri.py:99-107): [0..2] c0, b, d;
   // [3..5] c0 w_0 / 2, b w_1 / 2, d w_1 / 2 of g_i = sum_q (f_q w_q / 2) l_i(q) (w_1 = w_2 = w_3):
   // g_i = c0 w_0/2 f_0 + b w_1/2 (f_1 + f_2 + f_3) + d w_1/2 f_{q(i)}
+  // A launch of a SEP instantiation carries k [3..5] instead, k = c1 c3 the product of the factors behind
+  // the program's two functions (host: src_separable_factor): g_i is linear in f, so phase G evaluates the
+  // bare functions and the factors ride on the constants the shares are multiplied with anyway.
   T qsym[6];
   unsigned off_tverts;  // packed local vertex triples of the tiles' elements (source programs)
   // source programs: the launch walks positions [u_first, u_first + n_tiles) of the plan's chain
@@ -666,7 +669,7 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     for (int i = tid; i < 3 * acc_stride; i += kRingBlock) accs[i] = T(0);
 
   // SRC: the program, one operation per lane, for the whole launch
-  // (SEP: no lanes, what the passes need of the program are its first four constants and three bits)
+  // (SEP: no lanes, what the passes need of the program are its two push constants and three bits)
   SrcLanes<T> prog;
   if constexpr (SRC && !SEP) prog = src_load_lanes<T>(src_in_kernarg<T>(__builtin_offsetof(RingArgs<T>, src)));
   int sep_flags = 0;
@@ -812,7 +815,7 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     constexpr int kQ = QL > 0 ? QL : 1;
     T qs[3], hwq[kQ], lamq[3][kQ];
     if constexpr (QL == 4) {
-      if constexpr (kSrcTableLoads<T>) {
+      if constexpr (kSrcTableLoads<T>) {  // (SEP: the host has put the functions' factors on these three)
         const src_const_tab<T> t = src_kernarg_table<T>(__builtin_offsetof(RingArgs<T>, qsym));
 #pragma unroll
         for (int i = 0; i < 3; ++i) qs[i] = t[3 + i];

@@ -115,6 +115,11 @@ bool src_is_separable(const tfem_source_program *in, double coord_bound) {
   for (int i = 1; i <= 3; i += 2)
     if (in->ops[i] != TFEM_SRC_SIN && in->ops[i] != TFEM_SRC_COS) return false;
   if (in->ops[4] != TFEM_SRC_MUL) return false;
+  // the factor that rides on the share constants: it must say what the two factors say one after the other
+  const double c1 = in->consts[1], c3 = in->consts[3], k = src_separable_factor<double>(in);
+  if (!std::isfinite(k)) return false;
+  if (std::fpclassify(k) == FP_SUBNORMAL && std::fpclassify(c1) != FP_SUBNORMAL && std::fpclassify(c3) != FP_SUBNORMAL)
+    return false;
   uint8_t fast[kSrcMaxOps];
   return src_trig_proof(in, coord_bound, fast) == 2 && fast[1] && fast[3];
 }

@@ -54,8 +54,16 @@ int src_convert_proven(const tfem_source_program *in, double coord_bound, SrcPro
 // The separable form k U(a x) V(b y): true when the program is, after the proof at `coord_bound`, exactly
 //   PUSH_a(c0) F(c1) PUSH_b(c2) G(c3) MUL,  {a, b} = {X, Y},  F, G proven SIN / COS
 // (the manufactured-solution sources sin sin, sin cos, cos cos).  The fp64 launches with four points
-// evaluate such a program without the interpreter (src_separable).
+// evaluate such a program without the interpreter (src_separable), with k = c1 c3 (src_separable_factor)
+// folded into the constants of the shares.  A program whose k is not finite, or is subnormal while c1 and
+// c3 are not (the interpreter multiplies the factors into values of magnitude <= 1 one after the other and
+// may keep bits the product of the two alone has lost), is refused.
 bool src_is_separable(const tfem_source_program *in, double coord_bound);
+// k = c1 c3 of a separable program, formed in T
+template <typename T>
+T src_separable_factor(const tfem_source_program *in) {
+  return T(in->consts[1]) * T(in->consts[3]);
+}
 
 #if defined(__HIPCC__)
 
@@ -550,13 +558,16 @@ __device__ __forceinline__ void src_run_wide(const SrcLanes<T> &prog, const T *c
   for (int i = 0; i < N; ++i) out[i] = s0[i];
 }
 
-// Separable programs (host: src_is_separable), fp64 launches with four points: c1 F(c0 a) * c3 G(c2 b)
+// Separable programs (host: src_is_separable), fp64 launches with four points: U(c0 a) * V(c2 b)
 // written out -- no decode, no stack, and the coordinates come from the caller's registers, who read all
-// six of an element's once for both factors and the determinant.  The arithmetic is src_run_wide's,
-// operation for operation: the points as c * fma(l2, v2, fma(l1, v1, l0 * v0)) (see the note at its
-// coordinate pushes), the proven functions with their factor folded in, then the product.  A product
-// rounds the same in either operand order, so which coordinate the program pushes first only decides
-// where its constants sit.
+// six of an element's once for both factors and the determinant.  The points and the functions' range
+// reduction, polynomial and sign are src_run_wide's, operation for operation: the points as
+// c * fma(l2, v2, fma(l1, v1, l0 * v0)) (see the note at its coordinate pushes).  The factors c1, c3 behind
+// the functions are NOT applied here: g_i is linear in f, so the host folds k = c1 c3 into the three share
+// constants the caller multiplies with anyway (RingArgs::qsym) -- one operation less per sine than the
+// polynomial with the factor folded in (src_sin_poly_scaled), and f differs from the interpreter's by
+// roundings RELATIVE to each value (nothing the boundary's small sines amplify).  A product rounds the same
+// in either operand order, so which coordinate the program pushes first only decides where its constants sit.
 // What the kernel keeps of the program (one scalar register for the whole launch):
 constexpr int kSepYFirst = 1, kSepXCos = 2, kSepYCos = 4;
 
@@ -571,7 +582,7 @@ __device__ __forceinline__ int src_separable_flags(src_const_ptr<T> p) {
 }
 
 // `c_offset`, `lam_offset`: where SrcProgram::c and the table l_i(q) sit in the kernel-argument segment.
-// Each factor reads its two constants and the table there when it starts (scalar loads, src_kernarg_table):
+// Each factor reads its push constant and the table there when it starts (scalar loads, src_kernarg_table):
 // carried through the other factor's polynomials they would sit in spill lanes.  The branches are
 // wave-uniform.
 template <typename T, int NE>
@@ -581,7 +592,7 @@ __device__ __forceinline__ void src_separable(int flags, size_t c_offset, size_t
   constexpr int QL = 4, N = NE * QL;
   const src_const_tab<T> ct = src_kernarg_table<T>(c_offset);
   const int ix = (flags & kSepYFirst) ? 2 : 0;
-  const T cx = ct[ix], cfx = ct[ix + 1];
+  const T cx = ct[ix];
 #define TFEM_SRC_SEP_POINTS(dst, v, c)                                                             \
   {                                                                                                \
     const src_const_tab<T> ltab = src_kernarg_table<T>(lam_offset);                                \
@@ -596,22 +607,22 @@ __device__ __forceinline__ void src_separable(int flags, size_t c_offset, size_t
   TFEM_SRC_SEP_POINTS(out, px, cx)
   if (flags & kSepXCos) {
 #pragma unroll
-    for (int i = 0; i < N; ++i) out[i] = src_cos_fast_scaled(out[i], cfx);
+    for (int i = 0; i < N; ++i) out[i] = src_cos_fast(out[i]);
   } else {
 #pragma unroll
-    for (int i = 0; i < N; ++i) out[i] = src_sin_fast_scaled(out[i], cfx);
+    for (int i = 0; i < N; ++i) out[i] = src_sin_fast(out[i]);
   }
   T g[N];
   const src_const_tab<T> ct2 = src_kernarg_table<T>(c_offset);  // (a second opaque pointer: loaded here, not carried)
-  const T cy = ct2[2 - ix], cfy = ct2[3 - ix];
+  const T cy = ct2[2 - ix];
   TFEM_SRC_SEP_POINTS(g, py, cy)
 #undef TFEM_SRC_SEP_POINTS
   if (flags & kSepYCos) {
 #pragma unroll
-    for (int i = 0; i < N; ++i) g[i] = src_cos_fast_scaled(g[i], cfy);
+    for (int i = 0; i < N; ++i) g[i] = src_cos_fast(g[i]);
   } else {
 #pragma unroll
-    for (int i = 0; i < N; ++i) g[i] = src_sin_fast_scaled(g[i], cfy);
+    for (int i = 0; i < N; ++i) g[i] = src_sin_fast(g[i]);
   }
 #pragma unroll
   for (int i = 0; i < N; ++i) out[i] = out[i] * g[i];
