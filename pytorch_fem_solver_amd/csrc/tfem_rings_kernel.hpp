@@ -611,6 +611,19 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   const int clen = SRC ? a.chain_len : 1;
   const int u_end = a.u_first + a.n_tiles;
   const int block0 = SRC ? a.u_first / clen : 0;
+  // kTileDesc (the SEP instantiations): per-tile buffer descriptors for the plan loads of the tile loop, below.
+  // The plan and its length as the tile loop knows them: the kernel argument's, which these instantiations
+  // read again behind every phase G -- whatever reads the plan in the loop takes these (plan_now), so that the
+  // argument's own copy is not a second pointer alive across G.  Every other instantiation reads a.plan as before.
+  constexpr bool kTileDesc = SEP;
+  const unsigned char *plan_at = a.plan;
+  unsigned plan_room = a.plan_bytes;
+  auto plan_now = [&]() {
+    if constexpr (kTileDesc)
+      return plan_at;
+    else
+      return a.plan;
+  };
   // SRC, runs: the workgroup takes runs blockIdx, blockIdx + gridDim, ... of the plan's run list (with
   // gridDim = the number of runs: its own one) and walks their positions one after the other
   const bool balanced = SRC && a.n_runs > 0;
@@ -619,7 +632,7 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     while (run_at == run_end) {
       run += int(gridDim.x);
       if (run >= a.n_runs) return -1;
-      ring_const_i32 first = (ring_const_i32)(uintptr_t)(a.plan + a.off_runs);
+      ring_const_i32 first = (ring_const_i32)(uintptr_t)(plan_now() + a.off_runs);
       run_at = first[run];
       run_end = first[run + 1];
     }
@@ -627,7 +640,7 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   };
   auto tile_at = [&](int k) {
     if constexpr (SRC != 0) {
-      ring_const_i32 order = (ring_const_i32)(uintptr_t)(a.plan + a.off_chain);
+      ring_const_i32 order = (ring_const_i32)(uintptr_t)(plan_now() + a.off_chain);
       if (balanced) {  // called with k = 0, 1, 2, ...: the positions in the workgroup's order
         const int u = next_position();
         return u < 0 ? -1 : __builtin_amdgcn_readfirstlane(order[u]);
@@ -653,6 +666,25 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   ring_rsrc_t r_fout = ring_rsrc(a.fout, a.fout_bytes);
   constexpr unsigned kRecBytes = unsigned(4 * RingRec<SLOTS>::kWords);
   constexpr unsigned kNone = 0x3FFFFFFu;  // row / vertex index behind every array: loads give 0
+  // kTileDesc: the plan loads of a tile go through descriptors of their own, formed per tile and stream
+  // from wave-uniform values on the scalar unit: the base is the first entry the WAVE
+  // reads, num_records the number of entries it may read times their size.  A lane's offset is then a
+  // launch constant (lane * entry size; the elements 256 and 512 further on ride in the instruction's
+  // immediate offset) and a lane past the count is out of range by itself -- it receives zeros from the
+  // same range check that `kNone` relies on, without the add, compare, select and scale per load that
+  // moved it there.  Only voffset and the immediate take part: soffset stays 0.
+  // tile_rsrc: `count` entries of `size` bytes, the first one `first` entries into the plan section at byte `off`;
+  // clipped to the plan's end (nothing behind it is readable, as with r_plan), empty for count <= 0
+  // (signed minimum and maximum: the scalar unit has both, while the saturating unsigned subtraction hipcc
+  // makes of `room > at ? room - at : 0` exists on the vector unit only and turns every load that uses the
+  // descriptor into a waterfall loop; the plan is shorter than 2^31 bytes, tfem_ring_plan_build)
+  auto tile_rsrc = [&](unsigned off, int first, int count, int size) {
+    const unsigned at = off + unsigned(first * size);
+    const int room = int(plan_room - at), want = count * size;
+    const int fits = want < room ? want : room;
+    return ring_rsrc(plan_at + at, unsigned(fits > 0 ? fits : 0));
+  };
+  const unsigned lane_b2 = unsigned(lane) * 2u, lane_b4 = unsigned(lane) * 4u, lane_b16 = unsigned(lane) * 16u;
   if (FQ && tid < 4)  // the spare entries slots without a triangle read (times a zero determinant)
     gtab[3 * a.lds_elem + tid] = T(0);
   // SRC: the same LDS region holds the load-vector accumulators: THREE buffers (tile number modulo
@@ -689,6 +721,17 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   // vertex ids of a tile: the lane's own row vertex and halo vertex number tid.  With
   // consecutive-vertex tiles the own id is arithmetic on the descriptor.
   auto load_ids = [&](const RingDesc &d, unsigned &g_own, unsigned &g_halo) {
+    if constexpr (kTileDesc) {
+      if (CHUNK)
+        g_own = unsigned(d.gid0 + lane);
+      else
+        g_own = __builtin_amdgcn_raw_buffer_load_b32(tile_rsrc(a.off_gid, d.vert_off + d.row0, d.row1 - d.row0, 4u),
+                                                     lane_b4, 0, 0);
+      // halo vertex n_own + tid: the wave's 64 start at n_own + 64 wave
+      g_halo = __builtin_amdgcn_raw_buffer_load_b32(
+          tile_rsrc(a.off_gid, d.vert_off + d.n_own + 64 * wave, d.n_vert - d.n_own - 64 * wave, 4u), lane_b4, 0, 0);
+      return;
+    }
     const int r = d.row0 + lane;
     if (CHUNK)
       g_own = unsigned(d.gid0 + lane);
@@ -765,6 +808,16 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   // three rounds for every tile while the others run two.
   auto load_tverts = [&](const RingDesc &d, unsigned (&tv)[SRC ? kRingElemPerLane : 1], int rot) {
     if (!SRC) return;
+    if constexpr (kTileDesc) {
+      // the wave's elements start at 64 ((wave + rot) & 3); rounds 1 and 2 lie 1 and 2 KiB behind round 0
+      const int first = ((wave + rot) & (kRingWaves - 1)) << 6;
+      const ring_rsrc_t r_tv = tile_rsrc(a.off_tverts, d.tvert_off + first, d.n_tv - first, 4u);
+#pragma unroll
+      for (int j = 0; j < kRingElemPerLane; ++j)
+        tv[SRC ? j : 0] =
+            __builtin_amdgcn_raw_buffer_load_b32(r_tv, lane_b4 + unsigned(4 * j * kRingBlock), 0, kStreamLoadNT);
+      return;
+    }
     const int vtid = (((wave + rot) & (kRingWaves - 1)) << 6) + lane;
 #pragma unroll
     for (int j = 0; j < kRingElemPerLane; ++j) {
@@ -955,6 +1008,15 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   };
 
   auto load_tile = [&](const RingDesc &d, unsigned g_own, unsigned g_halo) {
+    if constexpr (kTileDesc) {  // SEP: no slot codes, the coordinates go to LDS by themselves (load_xy_lds)
+      static_assert(!kTileDesc || (!FQ && kCoordsToLds), "the per-tile descriptors cover the SEP launches' loads");
+      const int first = d.row_off + d.row0, n = d.row1 - d.row0;  // the wave's rows
+      ring_load_rec<SLOTS>(tile_rsrc(a.off_rows, first, n, kRecBytes), lane_b16 * (kRecBytes / 16u), rec_ld);
+      if (!CHUNK)
+        rowstart_ld = int(__builtin_amdgcn_raw_buffer_load_b32(tile_rsrc(a.off_rowstart, first, n, 4u), lane_b4, 0, 0));
+      hin_ld = __builtin_amdgcn_raw_buffer_load_b16(tile_rsrc(a.off_hin, first, n, 2u), lane_b2, 0, 0);
+      return;
+    }
     const int r = d.row0 + lane;
     const unsigned row = r < d.row1 ? unsigned(d.row_off + r) : kNone;
     ring_load_rec<SLOTS>(r_plan, a.off_rows + row * kRecBytes, rec_ld);
@@ -1085,7 +1147,8 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
         typedef const RingArgs<T> __attribute__((address_space(4))) *ring_kernargs;
         const ring_kernargs ka = (ring_kernargs)src_kernarg_table<char>(0);
         r_coords = ring_rsrc(ka->coords, ka->coords_bytes);
-        r_plan = ring_rsrc(ka->plan, ka->plan_bytes);
+        plan_at = ka->plan;  // the tiles' own plan descriptors (tile_rsrc) are formed from these two, behind
+        plan_room = ka->plan_bytes;  // this point
         r_vals = ring_rsrc(ka->vals, ka->vals_bytes);
         r_fout = ring_rsrc(ka->fout, ka->fout_bytes);
       }
@@ -1152,7 +1215,16 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     if (SRC) {
       // the buffer the NEXT tile fills: the tile two back filled it, the rows of the tile before this
       // one were its last readers (previous iteration, in front of its closing barrier)
-      for (int i = tid; i < acc_stride; i += kRingBlock) accs[a_next * acc_stride + i] = T(0);
+      if constexpr (kTileDesc) {
+        // two sums per lane and store (ds_write_b128): one store per lane for up to 510 vertex slots.
+        // acc_stride = lds_vert + 2 is even and the buffers start on 16 bytes (xy: 32 lds_vert bytes, the
+        // stage: 4 (64 (SLOTS + 1) + 2) entries), so the last pair ends where the buffer does
+        typedef T acc_pair __attribute__((ext_vector_type(2)));
+        acc_pair *clean = reinterpret_cast<acc_pair *>(accs + a_next * acc_stride);
+        for (int i = tid; 2 * i < acc_stride; i += kRingBlock) clean[i] = acc_pair{T(0), T(0)};
+      } else {
+        for (int i = tid; i < acc_stride; i += kRingBlock) accs[a_next * acc_stride + i] = T(0);
+      }
     }
     if (t_n >= 0) {
       park(dn, xy + (cur ^ 1) * 2 * a.lds_vert);
@@ -1229,7 +1301,7 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     t_n = t_nn;
     dn = dnn;
     t_nn = tile_at(k + 3);
-    if (t_nn >= 0) dnn = ring_desc<CHUNK>(a.plan, a.off_desc, t_nn, wave);
+    if (t_nn >= 0) dnn = ring_desc<CHUNK>(plan_now(), a.off_desc, t_nn, wave);
     cur ^= 1;
   }
 }
