@@ -458,6 +458,13 @@ class AssemblyEngine:
     def renumbered(self):
         return self._perm is not None
 
+    def dof_permutation(self):
+        """None, or the int64 tensor p of a renumbered engine: row / column k of csr_structure(),
+        and with it every position of the CSR values, belongs to DoF p[k] of the caller.  What
+        addresses the CSR values by the caller's ids (parallel.InterfaceExchange.from_partition)
+        composes it; per-DoF vectors leave the engine in the caller's numbering and need nothing."""
+        return self._perm
+
     def _dofs_out(self, vec):
         """A per-DoF vector of the engine -> the caller's numbering."""
         if self._perm is None or vec is None:
@@ -1752,18 +1759,28 @@ class AssemblyEngine:
             vals, f = self._assemble_tiles(alpha, beta, want_matrix=True, fq=fq)
         else:
             vals, f = self.bilinear(alpha, beta), self.load(fq)
-        if out is not None:  # kernels without an output argument: one device copy each
-            self._output(out[0], vals.numel(), "CSR values").copy_(vals.view(-1))
-            self._output(out[1], f.numel(), "load vector").copy_(f.view(-1))
-            return out[0], out[1]
+        if out is not None:
+            # kernels without an output argument: one device copy per buffer given; a None member
+            # of the pair is the kernel's own tensor, as on the ring path
+            if out[0] is not None:
+                self._output(out[0], vals.numel(), "CSR values").copy_(vals.view(-1))
+                vals = out[0]
+            if out[1] is not None:
+                self._output(out[1], f.numel(), "load vector").copy_(f.view(-1))
+                f = out[1]
         return vals, f
 
-    def load(self, fq):
-        """(N_dof,) vector of sum_q f_q phi_i dx_q; fq is (E, Q) on any device."""
+    def load(self, fq, out=None):
+        """(N_dof,) vector of sum_q f_q phi_i dx_q; fq is (E, Q) on any device.  ``out``: write
+        into this preallocated device buffer (one device copy off the ring path)."""
         # the vector alone: row form with the source values staged per tile (142 us at 1e7
         # elements) when the ring plan applies, the element-form tile kernel (149 us) otherwise
         if self.kernel != "tiles" and self._use_rings() and self.ring_plan()["fq_ok"]:
-            return self._assemble_rings(0.0, 0.0, fq, want_matrix=False)
+            return self._assemble_rings(0.0, 0.0, fq, want_matrix=False, out=(None, out))
+        if out is not None:
+            f = self.load(fq)
+            self._output(out, f.numel(), "load vector").copy_(f.view(-1))
+            return out
         if self.tile_plan() is not None:
             return self._assemble_tiles(0.0, 0.0, want_matrix=False, fq=fq)[1]
         d = self._inputs()

@@ -222,11 +222,18 @@ class InterfaceExchange:
     # ------------------------------------------------------------------ constructors
     @classmethod
     def from_partition(cls, mesh, element_order, bounds, rank, rowptr, colind, local_to_global,
-                       device, dtype, group=None):
+                       device, dtype, group=None, perm=None):
         """General element-range partition of ONE global mesh (BASELINE config 4).
 
         Every rank derives the same global interface numbering from the global
         connectivity, so no communication is needed to set up the exchange.
+
+        ``perm``: ``engine.dof_permutation()`` of the engine that ``rowptr, colind`` come from.
+        An engine that renumbered its shard stores the pattern and the CSR values in its own
+        numbering (row / column k is local vertex ``perm[k]``), so the matrix positions go
+        through ``local_to_global[perm]``; the vector leaves the engine in the caller's numbering
+        and keeps the plain ``local_to_global``.  A pattern that does not fit ``local_to_global``
+        (a renumbered engine's without its ``perm``) raises ValueError.
         """
         tri = np.asarray(mesh["triangles"], dtype=np.int64)
         n_global = int(np.asarray(mesh["vertices"]).shape[0])
@@ -249,12 +256,30 @@ class InterfaceExchange:
         l2g = np.asarray(local_to_global, dtype=np.int64)
         rowptr = np.asarray(rowptr, dtype=np.int64)
         row_of_entry = np.repeat(np.arange(rowptr.shape[0] - 1, dtype=np.int64), np.diff(rowptr))
-        gi, gj = l2g[row_of_entry], l2g[np.asarray(colind, dtype=np.int64)]
+        if rowptr.shape[0] - 1 != l2g.shape[0]:
+            raise ValueError("interface exchange: the local pattern and local_to_global differ in size")
+        k_l2g = l2g
+        if perm is not None:  # the pattern of an engine that renumbered its shard
+            perm = torch.as_tensor(perm).cpu().numpy().astype(np.int64)
+            if perm.shape != l2g.shape or not np.array_equal(np.sort(perm), np.arange(l2g.shape[0])):
+                raise ValueError("interface exchange: perm is not a permutation of the local vertices")
+            k_l2g = l2g[perm]
+        gi, gj = k_l2g[row_of_entry], k_l2g[np.asarray(colind, dtype=np.int64)]
         mine = np.nonzero(shared_vertex[gi] & shared_vertex[gj])[0]
-        k_pos = np.searchsorted(global_keys, gi[mine] * n_global + gj[mine])
+        k_pos = cls._positions(global_keys, gi[mine] * n_global + gj[mine], "matrix entry")
         f_idx = np.nonzero(shared_vertex[l2g])[0]
-        f_pos = np.searchsorted(shared_ids, l2g[f_idx])
+        f_pos = cls._positions(shared_ids, l2g[f_idx], "vertex")
         return cls(mine, k_pos, f_idx, f_pos, global_keys.size, shared_ids.size, device, dtype, group)
+
+    @staticmethod
+    def _positions(keys, want, what):
+        """Positions of `want` in the ascending `keys`; every one of them must be there."""
+        pos = np.searchsorted(keys, want)
+        if want.size and (keys.size == 0 or not np.array_equal(keys[np.minimum(pos, keys.size - 1)], want)):
+            raise ValueError(f"interface exchange: a shared {what} of the local pattern is not on the global "
+                             "interface -- the pattern is not in the numbering of local_to_global (an engine "
+                             "that renumbered its mesh: pass perm=engine.dof_permutation())")
+        return pos
 
     @classmethod
     def for_strips(cls, mesh, rank, world, engine, group=None):
@@ -263,7 +288,11 @@ class InterfaceExchange:
         of rank r+1, so the shared vertices are two runs of consecutive ids (a handful of
         the ring plan's tiles, contiguous pack / unpack).  Interface k (between ranks k and
         k+1) carries, for the n+1 row vertices, the diagonal entries, the 2n entries of the
-        horizontal edges and the n+1 vector entries."""
+        horizontal edges and the n+1 vector entries.  The strip's vertex ids address the engine's
+        pattern directly: an engine that renumbered its mesh is refused."""
+        if getattr(engine, "renumbered", False):
+            raise NotImplementedError("strip interfaces on an internally renumbered mesh: a strip's numbering has "
+                                      "locality by construction (TFEM_RENUMBER=0 keeps the caller's numbering)")
         n = int(round(np.sqrt(mesh["triangles"].shape[0] // 2)))
         nvx = n + 1
         csr = engine.csr_structure()

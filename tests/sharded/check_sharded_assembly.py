@@ -1,7 +1,9 @@
 """One rank of the sharded assembly (BASELINE config 4) on the GPU, end to end: shard of ONE mesh
 (Morton element ranges) or a strip, ring plan with the interface tiles first, the bench's
 two-stream step (interface rows + exchange on the exchange stream, the rest on the assembly stream),
-then every entry this rank holds against the operator of the WHOLE mesh assembled on the same GPU.
+then every entry this rank holds against the operator of the WHOLE mesh assembled on the same GPU
+(err_values, err_vector) and against the numpy oracle of the whole mesh (err_values_oracle,
+err_vector_oracle).
 
 Started by tests/test_hip_distributed.py under torch.distributed.run (gloo: several ranks share the
 one card of the test box; over RCCL the same code runs with --backend nccl).  Every rank prints one JSON
@@ -127,9 +129,24 @@ def main():
     # entry is shared; entries of interior rows of OTHER ranks do not exist in this pattern
     err_v = float((out[0] - want_v).abs().max() / want_v.abs().max())
     err_f = float((out[1] - want_f).abs().max() / want_f.abs().max())
+    # and against the numpy oracle of the whole mesh (the same measure): the whole-mesh launch above
+    # shares its kernels with the shards, an error common to both would cancel there
+    from oracle import assembly_oracle as orc
+
+    n_global = whole["vertices"].shape[0]
+    geo = orc.geometry(whole["vertices"][whole["triangles"]], 1, 3)
+    k_local = orc.integrate_local(1.0 * orc.integrand_stiffness(geo) + 0.5 * orc.integrand_mass(geo), geo["dx"])
+    o_rowptr, o_colind, o_slots = orc.csr_pattern(whole["triangles"], n_global)
+    o_vals = orc.assemble_csr_values(k_local, o_slots, o_colind.shape[0])
+    o_f = orc.assemble_linear(orc.integrate_local(orc.integrand_load(geo), geo["dx"]), whole["triangles"], n_global)
+    oracle_v = o_vals[parallel._csr_positions(o_rowptr, o_colind, l2g[rows], l2g[colind])]
+    oracle_f = o_f.reshape(-1)[np.asarray(l2g)]
+    err_v_oracle = float(np.abs(out[0].cpu().numpy() - oracle_v).max() / np.abs(oracle_v).max())
+    err_f_oracle = float(np.abs(out[1].cpu().numpy().reshape(-1) - oracle_f).max() / np.abs(oracle_f).max())
     result = json.dumps({"rank": rank, "world": world, "layout": args.layout, "n_local_vertices": int(nv), "mode": mode,
                          "priority_tiles": n_pri, "tiles": n_all, "interface_entries": int(ex.n_matrix + ex.n_vector),
-                         "err_values": err_v, "err_vector": err_f})
+                         "err_values": err_v, "err_vector": err_f,
+                         "err_values_oracle": err_v_oracle, "err_vector_oracle": err_f_oracle})
     if args.out_dir:
         with open(os.path.join(args.out_dir, f"rank{rank}.json"), "w") as fh:
             fh.write(result)

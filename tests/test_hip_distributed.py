@@ -1,5 +1,5 @@
 """BASELINE config 4 on the GPU with more than one rank (-m gpu): N processes of
-tests/dist/check_sharded_assembly.py under torch.distributed.run share the test box's one card and
+tests/sharded/check_sharded_assembly.py under torch.distributed.run share the test box's one card and
 exchange over gloo -- shards, ring plans with the interface tiles first, the two-stream step of
 bench.py, pack / all-reduce / unpack -- and every rank compares what it holds with the operator of
 the whole mesh (fp64, 1e-12).  Over RCCL (one rank per GPU) the same script runs with
@@ -16,7 +16,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCRIPT = os.path.join(REPO, "tests", "dist", "check_sharded_assembly.py")
+SCRIPT = os.path.join(REPO, "tests", "sharded", "check_sharded_assembly.py")
 
 
 def _free_port():
@@ -43,6 +43,7 @@ def test_sharded_assembly_with_interface_tiles_first(world, layout, tmp_path):
     ranks = _run(world, tmp_path, "--layout", layout)
     for r in ranks:
         assert r["err_values"] <= 1e-12 and r["err_vector"] <= 1e-12, r
+        assert r["err_values_oracle"] <= 1e-12 and r["err_vector_oracle"] <= 1e-12, r
         assert 0 < r["priority_tiles"] < r["tiles"], r
         assert r["interface_entries"] > 0
     assert len({r["interface_entries"] for r in ranks}) == 1  # one global interface numbering
@@ -56,6 +57,7 @@ def test_sharded_steps_of_the_bench(world, layout, stepper, tmp_path):
     ranks = _run(world, tmp_path, "--layout", layout, "--stepper", stepper)
     for r in ranks:
         assert r["err_values"] <= 1e-12 and r["err_vector"] <= 1e-12 and r["mode"] == "eager", r
+        assert r["err_values_oracle"] <= 1e-12 and r["err_vector_oracle"] <= 1e-12, r
 
 
 @pytest.mark.parametrize("stepper", ["graph", "graph-first"])
@@ -66,12 +68,13 @@ def test_steps_recorded_into_hip_graphs_over_rccl_one_rank(stepper, tmp_path):
     operator of the whole mesh."""
     ranks = _run(1, tmp_path, "--layout", "partition", "--backend", "nccl", "--stepper", stepper)
     assert ranks[0]["mode"] == "graph" and ranks[0]["err_values"] <= 1e-12 and ranks[0]["err_vector"] <= 1e-12, ranks
+    assert ranks[0]["err_values_oracle"] <= 1e-12 and ranks[0]["err_vector_oracle"] <= 1e-12, ranks
 
 
 def test_bench_default_scaling_is_config_4_and_one_rank_over_rccl_takes_graphs(tmp_path):
     """bench.py's N > 1 defaults: --scaling strong (BASELINE config 4).  And the whole N > 1 machinery
     with ONE rank over RCCL (torch.distributed.run, world size 1 is treated as N = 1 by bench.py, so
-    the check of the graph mode over RCCL is tests/dist/check_sharded_assembly.py above)."""
+    the check of the graph mode over RCCL is tests/sharded/check_sharded_assembly.py above)."""
     sys.path.insert(0, REPO)
     import bench
 

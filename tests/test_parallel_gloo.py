@@ -154,6 +154,66 @@ def test_weak_scaling_strips_exchange():
             assert n_matrix == 3 * 6 + 1 and n_vector == 7
 
 
+def test_from_partition_on_a_pattern_in_another_numbering():
+    """An engine that renumbered its shard hands out its CSR pattern (and values) in its own
+    numbering: row / column k is local vertex perm[k].  from_partition must refuse that pattern
+    without the permutation (its shared entries are not on the global interface) and, with it,
+    address the same global positions as for the pattern in the caller's numbering; the vector
+    positions do not change (the vector leaves the engine in the caller's numbering)."""
+    from pytorch_fem_solver_amd import meshgen, parallel
+
+    mesh = meshgen.delaunay_square(900, 4)
+    world = 3
+    order, bounds = parallel.partition_elements(mesh["vertices"], mesh["triangles"], world, "morton")
+    rng = np.random.default_rng(7)
+    cpu = torch.device("cpu")
+    for rank in range(world):
+        local, l2g = parallel.extract_shard(mesh, order[bounds[rank]:bounds[rank + 1]])
+        n = l2g.shape[0]
+        rowptr, colind, vals, _ = _local_system(local)
+        plain = parallel.InterfaceExchange.from_partition(mesh, order, bounds, rank, rowptr, colind, l2g, cpu, torch.float64)
+        assert plain.n_matrix > 0 and plain.k_idx.numel() > 0
+        perm = rng.permutation(n)
+        inv = np.empty_like(perm)
+        inv[perm] = np.arange(n)
+        p_rowptr, p_colind, _ = orc.csr_pattern(inv[local["triangles"]], n)
+        with pytest.raises(ValueError, match="dof_permutation"):
+            parallel.InterfaceExchange.from_partition(mesh, order, bounds, rank, p_rowptr, p_colind, l2g, cpu, torch.float64)
+        # position of every entry of the permuted pattern in the caller's pattern
+        p_rows = np.repeat(np.arange(n), np.diff(p_rowptr))
+        to_plain = parallel._csr_positions(rowptr, colind, perm[p_rows], perm[p_colind])
+        assert np.array_equal(np.sort(to_plain), np.arange(colind.shape[0]))
+        for given in (perm, torch.from_numpy(perm)):
+            ex = parallel.InterfaceExchange.from_partition(mesh, order, bounds, rank, p_rowptr, p_colind, l2g, cpu,
+                                                           torch.float64, perm=given)
+            assert (ex.n_matrix, ex.n_vector) == (plain.n_matrix, plain.n_vector)
+            by_pos, plain_by_pos = np.argsort(ex.k_pos.numpy()), np.argsort(plain.k_pos.numpy())
+            assert np.array_equal(ex.k_pos.numpy()[by_pos], plain.k_pos.numpy()[plain_by_pos])
+            assert np.array_equal(to_plain[ex.k_idx.numpy()[by_pos]], plain.k_idx.numpy()[plain_by_pos])
+            assert torch.equal(ex.f_idx, plain.f_idx) and torch.equal(ex.f_pos, plain.f_pos)
+        # the values of the permuted pattern pack into the buffer the caller's values pack into
+        p_vals = np.ascontiguousarray(vals[to_plain])
+        assert torch.equal(ex.pack(torch.from_numpy(p_vals)), plain.pack(torch.from_numpy(vals.copy())))
+        # the identity is a permutation like any other; a wrong one is refused
+        same = parallel.InterfaceExchange.from_partition(mesh, order, bounds, rank, rowptr, colind, l2g, cpu,
+                                                         torch.float64, perm=np.arange(n))
+        assert torch.equal(same.k_idx, plain.k_idx) and torch.equal(same.k_pos, plain.k_pos)
+        with pytest.raises(ValueError, match="permutation"):
+            parallel.InterfaceExchange.from_partition(mesh, order, bounds, rank, p_rowptr, p_colind, l2g, cpu,
+                                                      torch.float64, perm=np.zeros(n, dtype=np.int64))
+
+
+def test_for_strips_refuses_a_renumbered_engine():
+    from pytorch_fem_solver_amd import meshgen, parallel
+
+    strip = meshgen.structured_rectangle(6, 6, 0.0, 1.0, 0.0, 1.0, jitter=0.0)
+    rowptr, colind, _ = orc.csr_pattern(strip["triangles"], 49)
+    engine = _FakeEngine(rowptr, colind)
+    engine.renumbered = True
+    with pytest.raises(NotImplementedError, match="renumbered"):
+        parallel.InterfaceExchange.for_strips(strip, 0, 2, engine)
+
+
 def test_partition_helpers():
     from pytorch_fem_solver_amd import meshgen, parallel
 
