@@ -377,6 +377,40 @@ __device__ __forceinline__ void ring_store_run1(const T *stage, int total, int d
   }
 }
 
+// ring_store_run1 through a descriptor of the run's own (the SEP instantiations, consecutive-vertex tiles,
+// 7-slot records; fp64): `r_run` starts at the run's first CSR entry and is as long as the run's whole PAIRS
+// of entries (8 * (total & ~1) bytes, clipped to the array's end by the caller), so lane j of step u stores
+// its pair at 16 j + 1024 u, four launch constants, and the range check drops the lanes behind the run: no
+// offset arithmetic, no test, one 16-byte LDS read per step (the stage of a wave starts on 16 bytes).  An odd
+// run (7 x an odd number of rows) ends in a lone entry, which is in no pair: it goes through a descriptor of
+// its own (last_rsrc(), formed behind the wave-uniform test), which only lane 0's offset is inside.
+template <typename T, typename LastRsrc>
+__device__ __forceinline__ void ring_store_run1_desc(const T *stage, int total, ring_rsrc_t r_run, unsigned lane_b16,
+                                                     LastRsrc last_rsrc, int plain_stores) {
+  static_assert(sizeof(T) == 8, "pairs of doubles");
+  typedef T stage_pair __attribute__((ext_vector_type(2)));
+  const stage_pair *pairs = reinterpret_cast<const stage_pair *>(stage) + (threadIdx.x & 63);
+  constexpr int kSteps = 64 * 8 / 128;  // 7-slot records
+  stage_pair va[kSteps];
+#pragma unroll
+  for (int u = 0; u < kSteps; ++u) va[u] = pairs[64 * u];
+  // the launch's store policy (RingArgs::plain_stores), asked once for all steps
+  if (plain_stores & 1) {
+#pragma unroll
+    for (int u = 0; u < kSteps; ++u)
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ru32x4, va[u]), r_run, lane_b16 + unsigned(1024 * u), 0,
+                                             0);
+  } else {
+#pragma unroll
+    for (int u = 0; u < kSteps; ++u)
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ru32x4, va[u]), r_run, lane_b16 + unsigned(1024 * u), 0,
+                                             kStreamNT);
+  }
+  if (total & 1)  // eight bytes long: 16 j is inside for lane 0 alone
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ru32x2, stage[total - 1]), last_rsrc(), lane_b16, 0,
+                                          kStreamNT);
+}
+
 // One run per wave EXCEPT for long rows (plans of unstructured meshes: vertices with 8 .. 15
 // neighbours are written by k_p1_long_rows): their entries are not in the stage, the rows behind
 // them start further on in the CSR array.  `pre` = stage index of the lane's row, `csr` = CSR
@@ -618,6 +652,11 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   constexpr bool kTileDesc = SEP;
   const unsigned char *plan_at = a.plan;
   unsigned plan_room = a.plan_bytes;
+  T *vals_at = a.vals;  // the same for the value array (run_rsrc, below)
+  unsigned vals_room = a.vals_bytes;
+  // ... and for the store policy: asked of the argument itself, the answer is a launch constant that hipcc keeps
+  // in a scalar pair through G, at the price of two spilled scalars
+  int plain_now = a.plain_stores;
   auto plan_now = [&]() {
     if constexpr (kTileDesc)
       return plan_at;
@@ -684,6 +723,18 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
     const int fits = want < room ? want : room;
     return ring_rsrc(plan_at + at, unsigned(fits > 0 ? fits : 0));
   };
+  // run_rsrc: the same for a wave's run of CSR values, `count` entries from entry `first` of the value array.  The
+  // array may be longer than 2^31 bytes (the launch admits 2^32) but not than 2^31 entries, so the clipping is
+  // done in entries, with the signed minimum and maximum of tile_rsrc (an unsigned compare and select of byte
+  // counts came out as a vector subtraction with borrow, and the stores in waterfall loops); a run that starts
+  // behind the array's end is empty.
+  auto run_rsrc = [&](T *vals, unsigned vals_room, int first, int count) {
+    const int at = first > 0 ? first : 0;  // (nothing in front of the array either, whatever the plan says)
+    const int room = int(vals_room / unsigned(sizeof(T))) - at;
+    const int fits = count < room ? count : room;
+    return ring_rsrc(reinterpret_cast<unsigned char *>(vals) + unsigned(at) * unsigned(sizeof(T)),
+                     unsigned(fits > 0 ? fits : 0) * unsigned(sizeof(T)));
+  };
   const unsigned lane_b2 = unsigned(lane) * 2u, lane_b4 = unsigned(lane) * 4u, lane_b16 = unsigned(lane) * 16u;
   if (FQ && tid < 4)  // the spare entries slots without a triangle read (times a zero determinant)
     gtab[3 * a.lds_elem + tid] = T(0);
@@ -722,9 +773,9 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   // consecutive-vertex tiles the own id is arithmetic on the descriptor.
   auto load_ids = [&](const RingDesc &d, unsigned &g_own, unsigned &g_halo) {
     if constexpr (kTileDesc) {
-      if (CHUNK)
-        g_own = unsigned(d.gid0 + lane);
-      else
+      // CHUNK: no own id at all -- the coordinate load and the f store form their offsets from the
+      // descriptor's gid0 where they are issued (one shift-add each), nothing rides along from tile to tile
+      if (!CHUNK)
         g_own = __builtin_amdgcn_raw_buffer_load_b32(tile_rsrc(a.off_gid, d.vert_off + d.row0, d.row1 - d.row0, 4u),
                                                      lane_b4, 0, 0);
       // halo vertex n_own + tid: the wave's 64 start at n_own + 64 wave
@@ -1060,7 +1111,14 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
   auto load_xy_lds = [&](const RingDesc &d, unsigned g_own, unsigned g_halo, T *dst) {
     if constexpr (kCoordsToLds) {
       typedef __attribute__((address_space(3))) void *lds_ptr;
-      if (d.row0 + lane < d.row1)
+      if constexpr (kTileDesc && CHUNK) {
+        // consecutive vertices: the lane's offset is 16 (gid0 + lane), one shift-add on the lane number, and
+        // the lane test is against the wave's row count (a lane behind the rows must write nothing: the
+        // next wave's rows or the halo land there)
+        if (lane < d.row1 - d.row0)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(r_coords, (lds_ptr)(dst + 2 * d.row0), 16,
+                                                   (unsigned(lane) << 4) + unsigned(d.gid0) * 16u, 0, 0, 0);
+      } else if (d.row0 + lane < d.row1)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(r_coords, (lds_ptr)(dst + 2 * d.row0), 16, g_own * 16u, 0, 0, 0);
       if (d.n_own + tid < d.n_vert)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(r_coords, (lds_ptr)(dst + 2 * (d.n_own + 64 * wave)), 16,
@@ -1149,7 +1207,10 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
         r_coords = ring_rsrc(ka->coords, ka->coords_bytes);
         plan_at = ka->plan;  // the tiles' own plan descriptors (tile_rsrc) are formed from these two, behind
         plan_room = ka->plan_bytes;  // this point
-        r_vals = ring_rsrc(ka->vals, ka->vals_bytes);
+        vals_at = ka->vals;
+        vals_room = ka->vals_bytes;
+        plain_now = ka->plain_stores;
+        r_vals = ring_rsrc(vals_at, vals_room);
         r_fout = ring_rsrc(ka->fout, ka->fout_bytes);
       }
       // (the barrier behind G stands in front of the rows' read of their sums -- SEP: behind D --: the
@@ -1236,7 +1297,28 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
       }
     }
     if (KMAT) {
-      if (CHUNK) {  // one run per wave by construction, its CSR offset in the descriptor
+      if constexpr (kTileDesc && CHUNK && SLOTS == 7) {
+        // the same through a descriptor of the run's own (ring_store_run1_desc); a regular wave has no long
+        // row and does not look for one.  (7-slot records: with the eight steps of a 15-slot stage read ahead of
+        // the stores the K + f kernels need 187 registers and lose their third wave; they keep the code below.)
+        __builtin_amdgcn_wave_barrier();
+        bool holes = false;
+        if (!regular) {
+          const int k_row = rec.k();
+          const bool is_long = dc.row0 + lane < dc.row1 && k_row == 0 && (rec.w[3] >> 31) != 0u;
+          holes = __ballot(is_long) != 0ull;
+          if (holes) {
+            const int true_len = is_long ? int(rec.w[3] & 0x7FFFFFFFu) : k_row > 0 ? k_row + 1 : 0;
+            const int csr = dc.rs0 + wave_inclusive_scan(true_len) - true_len;
+            ring_store_pieces<T>(my_stage, total, pre, csr, is_long, r_vals);
+          }
+        }
+        if (!holes)
+          ring_store_run1_desc<T>(
+              my_stage, total, run_rsrc(vals_at, vals_room, dc.rs0, total & ~1), lane_b16,
+              [&]() { return run_rsrc(vals_at, vals_room, dc.rs0 + total - 1, 1); }, plain_now);
+        __builtin_amdgcn_wave_barrier();
+      } else if (CHUNK) {  // one run per wave by construction, its CSR offset in the descriptor
         __builtin_amdgcn_wave_barrier();
         // long rows (k = 0, bit 31 of the last record word, the row's length below it) leave holes
         const bool is_long = SLOTS == 7 && dc.row0 + lane < dc.row1 && kk == 0 && (rec.w[3] >> 31) != 0u;
@@ -1269,7 +1351,9 @@ __global__ __launch_bounds__(kRingBlock, (SRC && SLOTS == 7 && QL <= 4) ? 4 : (S
       facc = accs[a_cur * acc_stride + (my_row < dc.row1 ? my_row : a.lds_vert)] + accs[a_prev * acc_stride + from];
     }
     if (LOAD && dc.row0 + lane < dc.row1) {
-      const unsigned byte = gid_row * unsigned(sizeof(T));
+      // kTileDesc, consecutive vertices: the row's vertex is gid0 + lane (load_ids)
+      const unsigned byte = (kTileDesc && CHUNK) ? (unsigned(lane) << 3) + unsigned(dc.gid0) * 8u
+                                                 : gid_row * unsigned(sizeof(T));
       if constexpr (sizeof(T) == 8)
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ru32x2, facc), r_fout, byte, 0, kStreamNT);
       else
