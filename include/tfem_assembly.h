@@ -828,6 +828,34 @@ int tfem_mg_restrict_residual(const int32_t *ptr, const int32_t *idx, const void
 int tfem_mg_prolong_add(const int32_t *parents, const void *mask_f, const void *e_c, void *x_f,
                         int real_bytes, int64_t n_f, int64_t n_c, void *stream);
 
+/* The same three on a block of n_vec >= 1 vectors (csrc/tfem_mg_multi.hip).  x, b, ax, b_f, ax_f,
+ * r_c, e_c, x_f are n x n_vec reals, ROW-major: the n_vec values of a DoF are consecutive (the
+ * layout of tfem_p1_apply_rings_multi, tfem_csr_spmm and tfem_cg_*); w, the masks, ptr, idx and
+ * parents keep one entry per DoF.  One launch for any n_vec; n_vec == 1 IS the single launch above.
+ * smooth:   x[i][c] = w[i] * b[i][c], or x[i][c] = x[i][c] + w[i] * (b[i][c] - ax[i][c]); 16 bytes
+ *           per lane when x, b and ax are aligned to 16 bytes, whatever n_vec (w is read per value).
+ * restrict_residual: r_c[v][c] = mask_c[v] * 0.5 * sum_j mask_f[i_j] * (b_f[i_j][c] - ax_f[i_j][c]):
+ *           the eight lanes per row and the order of the single launch for every column; idx and
+ *           mask_f are read once per entry, one accumulator per column, at most 8 columns per pass.
+ * prolong_add: x_f[i][c] = x_f[i][c] + mask_f[i] * 0.5 * (e_c[a][c] + e_c[b][c]), (a, b) =
+ *           parents[i] read once per fine DoF.
+ * With n_vec 2, 4 or 8 and the blocks aligned to min(16, n_vec * real_bytes) bytes the rows move
+ * in accesses of that width, otherwise value by value.  Column c of every result is bit for bit
+ * what the single launch gives for the contiguous copy of column c; no fma, no atomics, two calls
+ * give the same bits.  An index of idx or parents outside its array reads 0 and touches nothing.
+ * Refusals as above, with the extents of the blocks n * n_vec * real_bytes (4 GiB or more:
+ * TFEM_ERR_INDEX_RANGE; the output overlapping an input anywhere in that extent:
+ * TFEM_ERR_INVALID_ARGUMENT), and n_vec < 1: TFEM_ERR_INVALID_ARGUMENT.  A size of 0 (n, n_c for
+ * restrict, n_f for prolong) succeeds and launches nothing. */
+int tfem_mg_smooth_multi(void *x, const void *b, const void *ax, const void *w, int real_bytes,
+                         int64_t n, int64_t n_vec, int first, void *stream);
+int tfem_mg_restrict_residual_multi(const int32_t *ptr, const int32_t *idx, const void *mask_c,
+                                    const void *mask_f, const void *b_f, const void *ax_f, void *r_c,
+                                    int real_bytes, int64_t n_c, int64_t n_f, int64_t n_vec,
+                                    void *stream);
+int tfem_mg_prolong_add_multi(const int32_t *parents, const void *mask_f, const void *e_c, void *x_f,
+                              int real_bytes, int64_t n_f, int64_t n_c, int64_t n_vec, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Interface exchange of the multi-GPU sharding (DEVICE; the path shards by element
  * range, DoFs on an inter-rank interface are summed with one all-reduce of a packed

@@ -24,39 +24,11 @@
 // the entry points refuse arrays of 4 GiB or more (check_extents).
 #include <hip/hip_runtime.h>
 
-#include "tfem_common.hpp"
-#include "tfem_rowkit.hpp"
+#include "tfem_mg.hpp"  // the launch shape, mg_load / mg_store, the host checks (shared with tfem_mg_multi.hip)
 
 #pragma clang fp contract(off)
 
 namespace tfem {
-
-constexpr int kMgBlock = 256;  // lanes per workgroup
-constexpr int kMgRowLanes = 8;  // lanes per row of P^T
-
-template <typename T, int N>
-using mg_vec = T __attribute__((ext_vector_type(N)));
-
-// Entry i of an array of T behind a buffer resource; 0 outside it.
-template <typename T>
-__device__ __forceinline__ T mg_load(ring_rsrc_t r, unsigned i) {
-  if constexpr (sizeof(T) == 8) {
-    // two dword loads: raw_buffer_load_b64 is miscompiled by this hipcc (tfem_tiles.hip)
-    const ru32x2 v{__builtin_amdgcn_raw_buffer_load_b32(r, i * 8u, 0, 0),
-                   __builtin_amdgcn_raw_buffer_load_b32(r, i * 8u + 4u, 0, 0)};
-    return __builtin_bit_cast(double, v);
-  } else {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, i * 4u, 0, 0));
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void mg_store(ring_rsrc_t r, unsigned i, T v) {
-  if constexpr (sizeof(T) == 8)
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ru32x2, v), r, i * 8u, 0, 0);
-  else
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, i * 4u, 0, 0);
-}
 
 // VEC: the four arrays are aligned to 16 bytes; a lane moves 16 bytes of each (2 doubles or 4
 // floats), the lanes behind the last whole group take the 1 .. 3 entries of the tail one by one.
@@ -145,29 +117,6 @@ __global__ __launch_bounds__(kMgBlock) void k_mg_prolong(const int32_t *__restri
   if (mask_f) v = mask_f[i] * v;
   mg_store<T>(r_x, i, mg_load<T>(r_x, i) + v);
 }
-
-// ---------------------------------------------------------------------------------------- host
-
-static bool mg_overlap(const void *a, int64_t a_bytes, const void *b, int64_t b_bytes) {
-  if (!a || !b || a_bytes <= 0 || b_bytes <= 0) return false;
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + uintptr_t(b_bytes) && pb < pa + uintptr_t(a_bytes);
-}
-
-static int mg_sizes(const char *name, int real_bytes, int64_t n_a, int64_t n_b) {
-  if (real_bytes != 4 && real_bytes != 8) return fail(TFEM_ERR_INVALID_ARGUMENT, "%s: real_bytes must be 4 or 8", name);
-  if (n_a < 0 || n_b < 0) return fail(TFEM_ERR_INVALID_ARGUMENT, "%s: negative size", name);
-  return TFEM_OK;
-}
-
-static int mg_launched(const char *name) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(TFEM_ERR_HIP, "%s launch: %s", name, hipGetErrorString(e));
-  return TFEM_OK;
-}
-
-// the largest n an extent check can be asked about without overflowing its own arithmetic
-constexpr int64_t kMgCountLimit = int64_t(1) << 40;
 
 }  // namespace tfem
 

@@ -6,7 +6,8 @@ P^T K P of the finer one (for coefficients that the quadrature integrates exactl
 differs by the quadrature error, which a preconditioner does not mind): no sparse triple product.
 Every level has its own ``Basis`` and its own matrix-free operator (``layout="operator"``), the
 transfers are the parent table of ``meshgen.refine_uniform`` and its transpose, and the vector part
-of the cycle runs in three kernels of libtfem_hip (csrc/tfem_mg.hip).
+of the cycle runs in three kernels of libtfem_hip (csrc/tfem_mg.hip; on a block of right-hand sides
+their block forms, csrc/tfem_mg_multi.hip: ``vcycle_multi``, ``solve_multi``).
 
     l = 0:  z[free] = K0[free, free]^-1 r[free], 0 elsewhere          (dense Cholesky, factored once)
     else:   x = w r;  (nu - 1) x  x += w (r - K x)                    w = omega * m / diag K
@@ -79,9 +80,17 @@ class GeometricMultigrid:
     ``engine``, ``n``), ``parents`` the parent tables of the refinements (``parents[l - 1]`` takes
     level l - 1 to level l).
 
+    Blocks (N, k) of right-hand sides go through ``vcycle_multi`` and ``solve_multi``: the same
+    number of launches per cycle whatever k is.  ``vcycle`` and ``solve`` take one vector.
+
     Refused with NotImplementedError: P2 elements, fracture bases, coefficient data
-    (``basis.coefficient``: its shape belongs to one mesh), a custom set of free DoFs, blocks of
-    right-hand sides; and a coarse mesh with more than ``Basis.DENSE_SOLVE_LIMIT`` free DoFs."""
+    (``basis.coefficient``: its shape belongs to one mesh), a custom set of free DoFs; and a coarse
+    mesh with more than ``Basis.DENSE_SOLVE_LIMIT`` free DoFs."""
+
+    #: ``vcycle_multi`` keeps the block buffers (x, K x, r per level, (n_l, k) each) of this many
+    #: widths k, the most recently used ones; an older width is dropped with the prepared launches
+    #: that point into its buffers and allocated again when it comes back.
+    BLOCK_WIDTHS_KEPT = 2
 
     def __init__(self, coarse_triangulation, levels, bilinear, quadrature_order=2, dirichlet=True, nu=2,
                  omega=2.0 / 3.0, dtype=None, *, element=None):
@@ -127,6 +136,7 @@ class GeometricMultigrid:
                                     None if l == 0 else self.levels[l - 1].n)
             self._factor_coarse(self.levels[0])
         self._applies = {}  # stream -> the prepared applies of the levels
+        self._blocks = {}  # k -> per level (x, ax, r) of shape (n_l, k); insertion order = age of last use
 
     # ------------------------------------------------------------------ set-up
     def _build_level(self, mesh, element, bilinear):
@@ -254,7 +264,8 @@ class GeometricMultigrid:
 
     def _vector(self, v, what):
         if _is_block(v):
-            raise NotImplementedError(f"GeometricMultigrid.{what}: blocks (N, k) of vectors; one vector (N,) or (N, 1)")
+            raise NotImplementedError(f"GeometricMultigrid.{what}: blocks (N, k) of vectors; one vector (N,) or (N, 1) "
+                                      f"(blocks: vcycle_multi, solve_multi)")
         flat = v.detach().to(self.device, self.dtype).reshape(-1)
         if flat.shape[0] != self.levels[-1].n:
             raise ValueError(f"GeometricMultigrid.{what}: {flat.shape[0]} entries, the finest level has "
@@ -320,6 +331,164 @@ class GeometricMultigrid:
                     p.mul_(rz_new / rz).add_(z)
                     rz = rz_new
         return top.engine._home(x).reshape(b.shape), it, res
+
+    # ------------------------------------------------------------------ blocks of right-hand sides
+    def _block_buffers(self, k):
+        """Per level (x, ax, r) of shape (n_l, k), zero on first use of the width k and reused; the
+        ``BLOCK_WIDTHS_KEPT`` most recently used widths are kept."""
+        buffers = self._blocks.pop(k, None)
+        if buffers is None:
+            buffers = [tuple(torch.zeros(level.n, k, dtype=self.dtype, device=self.device) for _ in range(3))
+                       for level in self.levels]
+            # behind the levels: the direction and its image of solve_multi, allocated by its first use
+            buffers.append(None)
+            if len(self._blocks) >= self.BLOCK_WIDTHS_KEPT:
+                self._blocks.pop(next(iter(self._blocks)))
+                # the prepared launches keep the buffers they point into: drop them with the width
+                # (those of the widths that stay are prepared again on their next use)
+                self._applies = {}
+        self._blocks[k] = buffers  # the youngest
+        return buffers
+
+    def _smooth_multi(self, level, buffers, k, first, stream):
+        x, ax, r = buffers
+        status = self._lib.tfem_mg_smooth_multi(_native.ptr(x), _native.ptr(r), None if first else _native.ptr(ax),
+                                                _native.ptr(level.w), self._real_bytes, level.n, k,
+                                                1 if first else 0, stream)
+        if status:
+            _native.check(status)
+
+    def _cycle_multi(self, l, buffers, k, applies, stream):
+        """``_cycle`` on the block buffers of the width k: r of level l -> x of level l."""
+        level, (x, ax, r) = self.levels[l], buffers[l]
+        if l == 0:
+            torch.mm(level.inverse, r, out=x)
+            return
+        coarse, apply, lib = self.levels[l - 1], applies[l], self._lib
+        coarse_x, _, coarse_r = buffers[l - 1]
+        self._smooth_multi(level, buffers[l], k, True, stream)
+        for _ in range(self.nu - 1):
+            apply(x, ax)
+            self._smooth_multi(level, buffers[l], k, False, stream)
+        apply(x, ax)
+        status = lib.tfem_mg_restrict_residual_multi(
+            _native.ptr(level.pt_ptr), _native.ptr(level.pt_idx), _native.ptr(coarse.mask), _native.ptr(level.mask),
+            _native.ptr(r), _native.ptr(ax), _native.ptr(coarse_r), self._real_bytes, coarse.n, level.n, k, stream)
+        if status:
+            _native.check(status)
+        self._cycle_multi(l - 1, buffers, k, applies, stream)
+        status = lib.tfem_mg_prolong_add_multi(_native.ptr(level.parents), _native.ptr(level.mask),
+                                               _native.ptr(coarse_x), _native.ptr(x), self._real_bytes, level.n,
+                                               coarse.n, k, stream)
+        if status:
+            _native.check(status)
+        for _ in range(self.nu):
+            apply(x, ax)
+            self._smooth_multi(level, buffers[l], k, False, stream)
+
+    def _block(self, V, what):
+        if V.dim() != 2 or V.shape[0] != self.levels[-1].n or V.shape[1] < 1:
+            raise ValueError(f"GeometricMultigrid.{what}: a block of shape ({self.levels[-1].n}, k) with k >= 1, "
+                             f"got {tuple(V.shape)}")
+        return V.detach().to(self.device, self.dtype)
+
+    def _vcycle_multi_into(self, R):
+        """The cycle on the block buffers of R's width; returns the buffer that holds the result
+        (valid until the next block cycle of that width)."""
+        k = int(R.shape[1])
+        buffers = self._block_buffers(k)
+        top = len(self.levels) - 1
+        buffers[top][2].copy_(R)
+        self._cycle_multi(top, buffers, k, self._level_applies(), _native.current_stream(self.device))
+        return buffers[top][0]
+
+    def vcycle_multi(self, R):
+        """One V-cycle on every column of ``R`` (N, k), k >= 1: Z (N, k) with column j the approximate
+        solution of K z = r_j on the free DoFs, 0 on the held ones.  The launches of ``vcycle``, each
+        on (n_l, k) row-major blocks: the block applies of the levels, the tfem_mg_*_multi kernels,
+        and one dense product on the coarsest level.  The block buffers are separate from those of
+        ``vcycle`` and kept for the ``BLOCK_WIDTHS_KEPT`` most recently used widths."""
+        block = self._block(R, "vcycle_multi")
+        with torch.cuda.device(self.device):
+            Z = self._vcycle_multi_into(block).clone()
+        return self.levels[-1].engine._home(Z)
+
+    def solve_multi(self, B, X0=None, rtol=1e-10, maxiter=100):
+        """``solve`` for the k columns of ``B`` (N, k) at once: k conjugate-gradient recurrences
+        preconditioned by ``vcycle_multi`` carried through one loop -- per iteration one block apply,
+        one block cycle, column-wise dot products, one alpha and one beta per column, and one host
+        read of the k relative residuals |r_j| / |m b_j|.  The contract of
+        ``conjugate_gradients_multi``: a column whose residual is <= rtol at a check is frozen from
+        then on -- its alpha and beta are 0 and its direction is zeroed, so its x and r stop
+        changing and no 0/0 arises (a column that starts converged, e.g. an all-zero one, takes no
+        iteration) -- and the loop ends when every column is frozen or after ``maxiter`` iterations.
+        The held DoFs keep X0's values (0 by default).  Returns (X (N, k), iterations (k,) int64,
+        relative residuals (k,)), the last two on the host; iterations[j] is the iteration at which
+        column j was frozen."""
+        top = self.levels[-1]
+        if B.dim() != 2 or B.shape[0] != top.n:
+            raise ValueError(f"GeometricMultigrid.solve_multi: B must have shape ({top.n}, k), got {tuple(B.shape)}")
+        rhs = self._block(B, "solve_multi")
+        n, k = rhs.shape
+        with torch.cuda.device(self.device):
+            # the blocks an apply is launched on are the kept ones of the width (a prepared launch
+            # keeps its two buffers): x and K x of the finest level, the direction and its image
+            buffers = self._block_buffers(k)
+            if buffers[-1] is None:
+                buffers[-1] = tuple(torch.empty(n, k, dtype=self.dtype, device=self.device) for _ in range(2))
+            P, AP = buffers[-1]
+            apply = self._level_applies()[-1]
+            mask = None if top.mask is None else top.mask.reshape(n, 1)
+            if X0 is None:
+                X = torch.zeros(n, k, dtype=self.dtype, device=self.device)
+            else:
+                if tuple(X0.shape) != (n, k):
+                    raise ValueError(f"GeometricMultigrid.solve_multi: X0 must have B's shape ({n}, {k})")
+                X = X0.detach().to(self.device, self.dtype).clone(memory_format=torch.contiguous_format)
+            if X0 is None:
+                R = rhs.clone(memory_format=torch.contiguous_format)
+            else:
+                top_x, top_ax, _ = buffers[len(self.levels) - 1]
+                top_x.copy_(X)
+                apply(top_x, top_ax)
+                R = rhs - top_ax
+            if mask is not None:
+                R *= mask
+            b_norm = torch.linalg.vector_norm(rhs if mask is None else mask * rhs, dim=0).clamp_min(
+                torch.finfo(self.dtype).tiny)
+            res = torch.linalg.vector_norm(R, dim=0) / b_norm
+            active = res > rtol  # (k,) on the device; its host copy decides the loop
+            running = active.cpu()
+            its = torch.zeros(k, dtype=torch.int64, device="cpu")
+            it = 0
+            if maxiter > 0 and bool(running.any()):
+                one, zero = torch.ones((), dtype=self.dtype, device=self.device), torch.zeros(k, dtype=self.dtype,
+                                                                                              device=self.device)
+                P.copy_(self._vcycle_multi_into(R))
+                rz = (R * P).sum(0)
+                P.mul_(active)
+                while True:
+                    apply(P, AP)
+                    if mask is not None:
+                        AP *= mask
+                    pap = (P * AP).sum(0)
+                    alpha = torch.where(active, rz / torch.where(active, pap, one), zero)
+                    X.add_(alpha * P)
+                    R.sub_(alpha * AP)
+                    it += 1
+                    res_new = torch.linalg.vector_norm(R, dim=0) / b_norm
+                    res = torch.where(active, res_new, res)  # a frozen column reports what froze it
+                    its[running] = it
+                    active = active & (res > rtol)
+                    running = active.cpu()  # the host read of the iteration
+                    if it >= maxiter or not bool(running.any()):
+                        break
+                    Z = self._vcycle_multi_into(R)
+                    rz_new = (R * Z).sum(0)
+                    beta = torch.where(active, rz_new / torch.where(active, rz, one), zero)
+                    P.mul_(beta).add_(Z * active)
+                    rz = torch.where(active, rz_new, rz)
+        return top.engine._home(X), its, res.cpu()
 
     def __repr__(self):
         sizes = ", ".join(str(level.n) for level in self.levels)
