@@ -856,6 +856,32 @@ int tfem_mg_restrict_residual_multi(const int32_t *ptr, const int32_t *idx, cons
 int tfem_mg_prolong_add_multi(const int32_t *parents, const void *mask_f, const void *e_c, void *x_f,
                               int real_bytes, int64_t n_f, int64_t n_c, int64_t n_vec, void *stream);
 
+/* The transfers between the P2 space and the P1 space of ONE mesh (csrc/tfem_mg_p2.hip): the step
+ * from a P2 level down to the P1 hierarchy above.  The P2 level has n_f = n_v + n_e DoFs, vertices
+ * first, then edges; edge DoF n_v + j has the endpoints edge_vertices[2 j], edge_vertices[2 j + 1]
+ * (n_e x 2 int32, vertex ids in either order).  P is the identity on the vertex rows and 0.5 / 0.5
+ * on an edge row.  Vectors, masks (NULL = all ones), real_bytes and stream as above; one launch
+ * each, no allocation, no synchronisation, no atomics, no fma: two calls give the same bits.
+ * restrict_residual: with d(j) = mask_f[j] * (b_f[j] - ax_f[j]),
+ *           r_c[v] = mask_c[v] * (d(v) + 0.5 * sum_{p in [ptr[v], ptr[v + 1])} d(idx[p])).
+ *           ptr (n_v + 1 int32), idx (2 n_e int32): row v lists the edge DoF ids (n_v already added)
+ *           of the edges at vertex v, ascending; a vertex without edges has an empty row.  Eight
+ *           lanes per row: lane s sums entries s, s + 8, ... in order, the partial sums are added
+ *           pairwise at distances 4, 2, 1, then d(v) is added to 0.5 x the sum.
+ * prolong_add: x_f[i] = x_f[i] + mask_f[i] * e_c[i] for i < n_v,
+ *           x_f[i] = x_f[i] + mask_f[i] * (0.5 * (e_c[a] + e_c[b])), (a, b) = edge_vertices[i - n_v],
+ *           for n_v <= i < n_f.  One lane per fine DoF.
+ * idx, edge_vertices and what they index are read through bounds-checked buffer accesses: an entry
+ * of idx >= n_f or an endpoint >= n_v counts as 0 and touches nothing.
+ * TFEM_ERR_INVALID_ARGUMENT: real_bytes not 4 or 8, a negative size, n_f < n_v, a NULL array that
+ * would be read or written, the output overlapping an input; TFEM_ERR_INDEX_RANGE: an array of
+ * 4 GiB or more.  Nothing is launched after a refusal; n_v == 0 succeeds and launches nothing. */
+int tfem_mg_p2_restrict_residual(const int32_t *ptr, const int32_t *idx, const void *mask_c,
+                                 const void *mask_f, const void *b_f, const void *ax_f, void *r_c,
+                                 int real_bytes, int64_t n_v, int64_t n_f, void *stream);
+int tfem_mg_p2_prolong_add(const int32_t *edge_vertices, const void *mask_f, const void *e_c, void *x_f,
+                           int real_bytes, int64_t n_v, int64_t n_f, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Interface exchange of the multi-GPU sharding (DEVICE; the path shards by element
  * range, DoFs on an inter-rank interface are summed with one all-reduce of a packed

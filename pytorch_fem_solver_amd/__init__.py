@@ -18,7 +18,7 @@ from .element import AbstractElement, ElementLine, ElementTri
 from .mesh import AbstractMesh, FracturesTri, MeshData, MeshesTri, MeshTri
 from .sparse import CSRMatrix, FormOperator
 from .basis.forms import CoefficientField
-from .multigrid import GeometricMultigrid
+from .multigrid import GeometricMultigrid, P2Multigrid
 
 __all__ = [
     "Basis",
@@ -33,6 +33,7 @@ __all__ = [
     "CSRMatrix",
     "FormOperator",
     "GeometricMultigrid",
+    "P2Multigrid",
     "CoefficientField",
     "meshgen",
 ]

@@ -16,6 +16,9 @@ their block forms, csrc/tfem_mg_multi.hip: ``vcycle_multi``, ``solve_multi``).
 
 with m the 0/1 mask of the level's interior DoFs.  The cycle is a symmetric positive definite
 operator (the post-smoothing is the adjoint of the pre-smoothing), so it may precondition CG.
+
+``P2Multigrid`` puts a P2 level on the finest mesh of such a hierarchy: P1 is a subspace of P2 on one
+mesh, the two transfers of that step are csrc/tfem_mg_p2.hip.
 """
 
 from __future__ import annotations
@@ -31,7 +34,7 @@ from .element import ElementTri
 from .mesh import MeshTri
 from .sparse import FormOperator, _into, _is_block
 
-__all__ = ["GeometricMultigrid"]
+__all__ = ["GeometricMultigrid", "P2Multigrid"]
 
 _MESH_KEYS = ("vertices", "vertex_markers", "triangles", "edges", "edge_markers", "neighbors")
 
@@ -46,6 +49,52 @@ def transpose_parents(parents, n_coarse):
     order = np.argsort(rows, kind="stable")  # `fine` ascends, a stable sort keeps it ascending per row
     ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n_coarse))])
     return ptr.astype(np.int32), fine[order].astype(np.int32)
+
+
+def transpose_edges(edge_vertices, n_vertices):
+    """(ptr (n_vertices + 1,), idx (2 n_edges,)) int32: row v lists the edge DoFs n_vertices + j of
+    the edges j with an endpoint v in ``edge_vertices`` (n_edges, 2), ascending.  With the weight 0.5
+    on every entry, plus the identity on the vertices, this is P^T of the step from P1 to P2 on one
+    mesh."""
+    ptr, idx = transpose_parents(edge_vertices, n_vertices)
+    return ptr, (idx + np.int32(n_vertices)).astype(np.int32)
+
+
+def _cycle_pcg(apply, cycle, mask, rhs, x0, rtol, maxiter):
+    """Conjugate gradients on K x = rhs preconditioned by ``cycle``, the loop of ``solve``: ``apply(u,
+    out)`` writes K u, ``cycle(r)`` returns the buffer that holds the V-cycle of r, ``mask`` is the
+    0/1 vector of the free DoFs (None: all), every vector in one numbering.  ``x0`` (None: zero) is
+    copied.  Returns (x, iterations, |r| / |m rhs|), the residual checked every iteration."""
+    x = torch.zeros_like(rhs) if x0 is None else x0.clone()
+    ap = torch.empty_like(rhs)
+    if x0 is None:
+        r = rhs.clone()
+    else:
+        apply(x, ap)
+        r = rhs - ap
+    if mask is not None:
+        r *= mask
+    b_norm = torch.linalg.vector_norm(rhs if mask is None else mask * rhs).clamp_min(torch.finfo(rhs.dtype).tiny)
+    it, res = 0, float(torch.linalg.vector_norm(r) / b_norm)
+    if res > rtol and maxiter > 0:
+        p = cycle(r).clone()
+        rz = torch.dot(r, p)
+        while True:
+            apply(p, ap)
+            if mask is not None:
+                ap *= mask
+            alpha = rz / torch.dot(p, ap)
+            x.add_(alpha * p)
+            r.sub_(alpha * ap)
+            it += 1
+            res = float(torch.linalg.vector_norm(r) / b_norm)
+            if res <= rtol or it >= maxiter:
+                break
+            z = cycle(r)
+            rz_new = torch.dot(r, z)
+            p.mul_(rz_new / rz).add_(z)
+            rz = rz_new
+    return x, it, res
 
 
 class _Level:
@@ -83,7 +132,7 @@ class GeometricMultigrid:
     Blocks (N, k) of right-hand sides go through ``vcycle_multi`` and ``solve_multi``: the same
     number of launches per cycle whatever k is.  ``vcycle`` and ``solve`` take one vector.
 
-    Refused with NotImplementedError: P2 elements, fracture bases, coefficient data
+    Refused with NotImplementedError: P2 elements (``P2Multigrid``), fracture bases, coefficient data
     (``basis.coefficient``: its shape belongs to one mesh), a custom set of free DoFs; and a coarse
     mesh with more than ``Basis.DENSE_SOLVE_LIMIT`` free DoFs."""
 
@@ -104,7 +153,8 @@ class GeometricMultigrid:
             raise TypeError("GeometricMultigrid: the coarse mesh is a triangle-format dictionary with the keys "
                             + ", ".join(_MESH_KEYS))
         if element is not None and getattr(element, "polynomial_order", 1) != 1:
-            raise NotImplementedError("GeometricMultigrid: P2 elements (the transfers are those of nested P1 spaces)")
+            raise NotImplementedError("GeometricMultigrid: P2 elements (the transfers are those of nested P1 spaces; "
+                                      "P2Multigrid puts a P2 level on top of this hierarchy)")
         levels, nu = int(levels), int(nu)
         if levels < 0 or nu < 1:
             raise ValueError("GeometricMultigrid: levels >= 0 and nu >= 1")
@@ -298,38 +348,8 @@ class GeometricMultigrid:
         top = self.levels[-1]
         rhs = self._vector(b, "solve")
         with torch.cuda.device(self.device):
-            apply = self._level_applies()[-1]
-            mask = top.mask
-            x = torch.zeros_like(rhs) if x0 is None else self._vector(x0, "solve").clone()
-            ap = torch.empty_like(rhs)
-            if x0 is None:
-                r = rhs.clone()
-            else:
-                apply(x, ap)
-                r = rhs - ap
-            if mask is not None:
-                r *= mask
-            b_norm = torch.linalg.vector_norm(rhs if mask is None else mask * rhs).clamp_min(
-                torch.finfo(self.dtype).tiny)
-            it, res = 0, float(torch.linalg.vector_norm(r) / b_norm)
-            if res > rtol and maxiter > 0:
-                p = self._vcycle_into(r).clone()
-                rz = torch.dot(r, p)
-                while True:
-                    apply(p, ap)
-                    if mask is not None:
-                        ap *= mask
-                    alpha = rz / torch.dot(p, ap)
-                    x.add_(alpha * p)
-                    r.sub_(alpha * ap)
-                    it += 1
-                    res = float(torch.linalg.vector_norm(r) / b_norm)
-                    if res <= rtol or it >= maxiter:
-                        break
-                    z = self._vcycle_into(r)
-                    rz_new = torch.dot(r, z)
-                    p.mul_(rz_new / rz).add_(z)
-                    rz = rz_new
+            x, it, res = _cycle_pcg(self._level_applies()[-1], self._vcycle_into, top.mask, rhs,
+                                    None if x0 is None else self._vector(x0, "solve"), rtol, maxiter)
         return top.engine._home(x).reshape(b.shape), it, res
 
     # ------------------------------------------------------------------ blocks of right-hand sides
@@ -493,4 +513,199 @@ class GeometricMultigrid:
     def __repr__(self):
         sizes = ", ".join(str(level.n) for level in self.levels)
         return (f"GeometricMultigrid({len(self.levels) - 1} refinements: {sizes} DoFs, V({self.nu},{self.nu}), "
+                f"omega={self.omega:.3g}, dtype={self.dtype})")
+
+
+class P2Multigrid:
+    """V(nu, nu)-cycle and multigrid-preconditioned CG for a P2 form: a P2 level on the finest mesh
+    of a P1 hierarchy (p-coarsening first, then the h-hierarchy of ``GeometricMultigrid``).
+
+    P1 is a subspace of P2 on one mesh and both spaces are discretised from the same callable, so
+    the P1 operator of the finest mesh IS the Galerkin operator P^T K2 P of the P2 one: no triple
+    product here either.  P is the identity on the vertex DoFs and 0.5 / 0.5 on an edge DoF (the
+    P2 numbering is "vertices, then edges"); the two transfers are csrc/tfem_mg_p2.hip.
+
+        x = w r;  (nu - 1) x  x += w (r - K x)                  w = omega * m2 / diag K2
+        r1 = m1 P^T( m2 (r - K x) )                              tfem_mg_p2_restrict_residual
+        e1 = the P1 V-cycle of r1                                GeometricMultigrid, its own buffers
+        x += m2 P e1                                             tfem_mg_p2_prolong_add
+        nu x  x += w (r - K x)                                   tfem_mg_smooth
+
+    The arguments are those of ``GeometricMultigrid`` (``levels`` refinements below the mesh that
+    carries the P2 level, 0 allowed; ``quadrature_order`` of both elements).  ``p1`` is the P1
+    hierarchy, ``basis`` the P2 ``Basis`` of its finest mesh (assemble the right-hand side with it),
+    ``operator`` its ``FormOperator`` -- ``layout="matrix_free"`` where the basis grants it, the
+    assembled CSR otherwise --, ``levels`` the P1 levels and then the P2 level.
+
+    A matrix-free P2 operator is applied in the ENGINE's numbering (the engine renumbers the edge
+    DoFs of a basis from 50,000 DoFs on; the vertex ids stay those of the P1 level): the tables,
+    masks and weights of the P2 level are built in that numbering and vectors cross once at the
+    boundary of ``vcycle`` / ``solve``.
+
+    Refused with NotImplementedError: what ``GeometricMultigrid`` refuses, blocks (N, k) of vectors
+    (``vcycle_multi`` / ``solve_multi`` are not built for P2) and a custom set of free DoFs."""
+
+    def __init__(self, coarse_triangulation, levels, bilinear, quadrature_order=3, dirichlet=True, nu=2,
+                 omega=2.0 / 3.0, dtype=None):
+        self.p1 = GeometricMultigrid(coarse_triangulation, levels, bilinear, quadrature_order, dirichlet, nu, omega,
+                                     dtype)
+        self.nu, self.omega, self.dirichlet = self.p1.nu, self.p1.omega, self.p1.dirichlet
+        self.device, self.dtype = self.p1.device, self.p1.dtype
+        self._lib, self._real_bytes = self.p1._lib, self.p1._real_bytes
+        mesh = self.p1.levels[-1].triangulation
+        previous = torch.get_default_dtype()
+        torch.set_default_dtype(self.dtype)
+        try:  # an element keeps tables in the default dtype of its creation
+            element = ElementTri(polynomial_order=2, integration_order=int(quadrature_order))
+            top = self._build_level(mesh, element, bilinear)
+        finally:
+            torch.set_default_dtype(previous)
+        self.basis, self.operator = top.basis, top.op
+        self.levels = self.p1.levels + [top]
+        with torch.cuda.device(self.device):
+            self._prepare_level(top, mesh)
+        self._applies = {}  # stream -> the prepared apply of the P2 level
+
+    # ------------------------------------------------------------------ set-up
+    @staticmethod
+    def _build_level(mesh, element, bilinear):
+        basis = Basis(MeshTri(triangulation=mesh), element)
+        expr = forms.trace(bilinear, basis, (), {})
+        try:
+            op = basis._bilinear_of(expr, "matrix_free")
+        except NotImplementedError:
+            op = basis._bilinear_of(expr, "operator")
+        if not isinstance(op, FormOperator):
+            raise TypeError("P2Multigrid: the bilinear form did not give an operator")
+        return _Level(mesh, basis, op)
+
+    def _prepare_level(self, level, mesh):
+        dev, dtype, n, engine = self.device, self.dtype, level.n, level.engine
+        n_v = int(np.asarray(mesh["vertices"]).shape[0])
+        edges = np.asarray(mesh["edges"]).reshape(-1, 2)
+        if n != n_v + edges.shape[0]:
+            raise ValueError(f"P2Multigrid: {n} P2 DoFs on a mesh of {n_v} vertices and {edges.shape[0]} edges")
+        level.n_v = n_v
+        # the numbering the level runs in: the engine's for the matrix-free launch (vertex ids are the
+        # caller's, edge DoF n_v + j of the engine is the caller's _perm[n_v + j]), the caller's otherwise
+        level.crossing = bool(level.op.matrix_free and engine.renumbered)
+        inward = engine._dofs_in if level.crossing else (lambda v: v)
+        if level.crossing:
+            perm = engine._perm.cpu().numpy()
+            if not (perm[:n_v] == np.arange(n_v)).all():
+                raise NotImplementedError("P2Multigrid: an engine that renumbers the vertex DoFs of a P2 basis")
+            edges = edges[perm[n_v:] - n_v]
+        diag = inward(level.op.diagonal().to(dev, dtype).reshape(-1))
+        if self.dirichlet:
+            level.free = level.basis._basis_parameters["inner_dofs"].to(dev).reshape(-1).long()
+            mask = torch.zeros(n, dtype=dtype, device=dev)
+            mask[level.free] = 1
+            level.mask = inward(mask).contiguous()
+            w = level.mask / torch.where(diag != 0, diag, torch.ones_like(diag))
+        else:
+            level.free, level.mask = None, None
+            w = 1.0 / diag
+        level.w = (self.omega * w).contiguous()
+        level.x, level.ax, level.r = (torch.zeros(n, dtype=dtype, device=dev) for _ in range(3))
+        ptr, idx = transpose_edges(edges, n_v)
+        level.edge_vertices = torch.as_tensor(np.ascontiguousarray(edges, dtype=np.int32), device=dev)
+        level.pt_ptr = torch.as_tensor(ptr, device=dev)
+        level.pt_idx = torch.as_tensor(idx, device=dev)
+
+    def _apply_of(self, level):
+        """``apply(u, out)``: out = K2 u on the level's buffers, in the numbering of the level."""
+        op = level.op
+        if op.matrix_free:
+            return op._rows_into()
+        csr = op.to_csr().to(self.device)
+        if csr.perm is None:
+            return _into(csr._prepared_spmv)
+
+        def through_matvec(u, out):
+            out.copy_(op.matvec(u))
+
+        return through_matvec
+
+    def _top_apply(self):
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        apply = self._applies.get(key)
+        if apply is None:
+            apply = self._applies[key] = self._apply_of(self.levels[-1])
+        return apply
+
+    # ------------------------------------------------------------------ the cycle
+    def _cycle(self, apply, stream):
+        level, coarse, lib, smooth = self.levels[-1], self.p1.levels[-1], self._lib, self.p1._smooth
+        smooth(level, True, stream)
+        for _ in range(self.nu - 1):
+            apply(level.x, level.ax)
+            smooth(level, False, stream)
+        apply(level.x, level.ax)
+        status = lib.tfem_mg_p2_restrict_residual(
+            _native.ptr(level.pt_ptr), _native.ptr(level.pt_idx), _native.ptr(coarse.mask), _native.ptr(level.mask),
+            _native.ptr(level.r), _native.ptr(level.ax), _native.ptr(coarse.r), self._real_bytes, level.n_v, level.n,
+            stream)
+        if status:
+            _native.check(status)
+        self.p1._cycle(len(self.p1.levels) - 1, self.p1._level_applies(), stream)
+        status = lib.tfem_mg_p2_prolong_add(_native.ptr(level.edge_vertices), _native.ptr(level.mask),
+                                            _native.ptr(coarse.x), _native.ptr(level.x), self._real_bytes, level.n_v,
+                                            level.n, stream)
+        if status:
+            _native.check(status)
+        for _ in range(self.nu):
+            apply(level.x, level.ax)
+            smooth(level, False, stream)
+
+    def _vector(self, v, what):
+        """``v`` as a flat vector of the hierarchy's type in the numbering of the P2 level."""
+        top = self.levels[-1]
+        if _is_block(v):
+            raise NotImplementedError(f"P2Multigrid.{what}: blocks (N, k) of vectors; one vector (N,) or (N, 1) "
+                                      f"(vcycle_multi and solve_multi are not built for P2)")
+        flat = v.detach().to(self.device, self.dtype).reshape(-1)
+        if flat.shape[0] != top.n:
+            raise ValueError(f"P2Multigrid.{what}: {flat.shape[0]} entries, the P2 level has {top.n} DoFs")
+        return top.engine._dofs_in(flat) if top.crossing else flat
+
+    def _result(self, x, like):
+        top = self.levels[-1]
+        if top.crossing:
+            x = top.engine._dofs_out(x)
+        return top.engine._home(x).reshape(like.shape)
+
+    def _vcycle_into(self, r):
+        """The cycle on the P2 level's buffers, r in the level's numbering; returns the buffer that
+        holds the result (valid until the next cycle)."""
+        top = self.levels[-1]
+        top.r.copy_(r)
+        self._cycle(self._top_apply(), _native.current_stream(self.device))
+        return top.x
+
+    def vcycle(self, r):
+        """One V-cycle on the residual ``r`` ((N,) or (N, 1), the DoFs of ``basis``): the approximate
+        solution z of K z = r on the free DoFs, 0 on the held ones; shaped like r."""
+        flat = self._vector(r, "vcycle")
+        with torch.cuda.device(self.device):
+            z = self._vcycle_into(flat).clone()
+        return self._result(z, r)
+
+    def solve(self, b, x0=None, rtol=1e-10, maxiter=100, free=None):
+        """Conjugate gradients preconditioned by ``vcycle`` for K x = b on the free DoFs: the contract
+        and the recurrence of ``GeometricMultigrid.solve`` (the held DoFs keep x0's values, 0 by
+        default; |r| / |m b| is checked every iteration).  Returns (x shaped like b, iterations,
+        relative residual)."""
+        if free is not None:
+            raise NotImplementedError("P2Multigrid.solve: a custom set of free DoFs; the hierarchy holds the boundary "
+                                      "DoFs of every level (dirichlet=True) or none")
+        rhs = self._vector(b, "solve")
+        start = None if x0 is None else self._vector(x0, "solve")
+        with torch.cuda.device(self.device):
+            x, it, res = _cycle_pcg(self._top_apply(), self._vcycle_into, self.levels[-1].mask, rhs, start, rtol,
+                                    maxiter)
+        return self._result(x, b), it, res
+
+    def __repr__(self):
+        sizes = ", ".join(str(level.n) for level in self.levels)
+        return (f"P2Multigrid(P2 over {len(self.p1.levels) - 1} refinements: {sizes} DoFs, V({self.nu},{self.nu}), "
                 f"omega={self.omega:.3g}, dtype={self.dtype})")

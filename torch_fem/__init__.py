@@ -15,6 +15,7 @@ from pytorch_fem_solver_amd import (  # noqa: F401
     InteriorEdgesFractureBasis,
     MeshesTri,
     MeshTri,
+    P2Multigrid,
 )
 
 __all__ = [
@@ -28,4 +29,5 @@ __all__ = [
     "MeshTri",
     "CoefficientField",
     "GeometricMultigrid",
+    "P2Multigrid",
 ]
