@@ -4,10 +4,8 @@ V-cycle on it and conjugate gradients preconditioned by that cycle.
 The spaces are nested, so the form re-discretised on a coarser mesh IS the Galerkin operator
 P^T K P of the finer one (for coefficients that the quadrature integrates exactly; otherwise it
 differs by the quadrature error, which a preconditioner does not mind): no sparse triple product.
-Every level has its own ``Basis`` and its own matrix-free operator (``layout="operator"``), the
-transfers are the parent table of ``meshgen.refine_uniform`` and its transpose, and the vector part
-of the cycle runs in three kernels of libtfem_hip (csrc/tfem_mg.hip; on a block of right-hand sides
-their block forms, csrc/tfem_mg_multi.hip: ``vcycle_multi``, ``solve_multi``).
+Every level has its own ``Basis`` and its own matrix-free operator (``layout="operator"``), and the
+transfers are the parent table of ``meshgen.refine_uniform`` and its transpose.
 
     l = 0:  z[free] = K0[free, free]^-1 r[free], 0 elsewhere          (dense Cholesky, factored once)
     else:   x = w r;  (nu - 1) x  x += w (r - K x)                    w = omega * m / diag K
@@ -17,8 +15,14 @@ their block forms, csrc/tfem_mg_multi.hip: ``vcycle_multi``, ``solve_multi``).
 with m the 0/1 mask of the level's interior DoFs.  The cycle is a symmetric positive definite
 operator (the post-smoothing is the adjoint of the pre-smoothing), so it may precondition CG.
 
-``P2Multigrid`` puts a P2 level on the finest mesh of such a hierarchy: P1 is a subspace of P2 on one
-mesh, the two transfers of that step are csrc/tfem_mg_p2.hip.
+The cycle is written once (``_Hierarchy._cycle``) over a list of levels, a list of their (x, K x, r)
+buffers and a list of their applies.  A level makes the three vector launches of libtfem_hip itself:
+its sweep, the restriction of its residual to the level below and the prolongation from there.  An
+h-level (``_Level``) runs them on single vectors (csrc/tfem_mg.hip) or on (n_l, k) blocks of
+right-hand sides (csrc/tfem_mg_multi.hip: ``vcycle_multi``, ``solve_multi``).  ``P2Multigrid`` puts
+a P2 level (``_P2Level``) on the finest mesh of such a hierarchy: P1 is a subspace of P2 on one
+mesh, the two transfers of that step are csrc/tfem_mg_p2.hip, and below it the same cycle goes on
+through the P1 levels.
 """
 
 from __future__ import annotations
@@ -37,6 +41,11 @@ from .sparse import FormOperator, _into, _is_block
 __all__ = ["GeometricMultigrid", "P2Multigrid"]
 
 _MESH_KEYS = ("vertices", "vertex_markers", "triangles", "edges", "edge_markers", "neighbors")
+_ptr = _native.ptr
+
+
+def _identity(v):
+    return v
 
 
 def transpose_parents(parents, n_coarse):
@@ -98,7 +107,15 @@ def _cycle_pcg(apply, cycle, mask, rhs, x0, rtol, maxiter):
 
 
 class _Level:
-    """What the cycle needs of one mesh of the hierarchy (attributes set by GeometricMultigrid)."""
+    """One mesh of the hierarchy, a P1 level: what the cycle needs of it (``free``, ``mask``, ``w``,
+    the single-vector buffers ``x``, ``ax``, ``r``: set by ``_Hierarchy._prepare_level``) and the
+    three vector launches of the cycle on it.  Each launch takes the level's (x, K x, r) buffers --
+    and those of the level below for a transfer -- and their width ``k``: None for vectors (n_l,),
+    the number of columns for (n_l, k) blocks (k = 1 included), which go through the block kernels."""
+
+    order = 1
+    #: True: the level runs in the engine's numbering and vectors cross at the hierarchy's boundary
+    crossing = False
 
     def __init__(self, triangulation, basis, op):
         self.triangulation = triangulation
@@ -107,12 +124,266 @@ class _Level:
         self.engine = basis._engine
         self.n = int(op.shape[0])
 
+    def set_coarser(self, coarse, parents, device):
+        """The transfers to and from ``coarse``, the level below: the parent table of the refinement
+        (P) and its transpose (P^T)."""
+        ptr, idx = transpose_parents(parents, coarse.n)
+        self.coarse = coarse
+        self.parents = torch.as_tensor(np.ascontiguousarray(parents, dtype=np.int32), device=device)
+        self.pt_ptr = torch.as_tensor(ptr, device=device)
+        self.pt_idx = torch.as_tensor(idx, device=device)
+
+    def smooth(self, buffers, k, first, stream):
+        """x = w r (``first``) or x += w (r - K x)."""
+        x, ax, r = buffers
+        if k is None:
+            status = self.lib.tfem_mg_smooth(_ptr(x), _ptr(r), None if first else _ptr(ax), _ptr(self.w),
+                                             self.real_bytes, self.n, 1 if first else 0, stream)
+        else:
+            status = self.lib.tfem_mg_smooth_multi(_ptr(x), _ptr(r), None if first else _ptr(ax), _ptr(self.w),
+                                                   self.real_bytes, self.n, k, 1 if first else 0, stream)
+        if status:
+            _native.check(status)
+
+    def restrict_residual(self, buffers, coarser, k, stream):
+        """r of the level below = m_c P^T( m (r - K x) )."""
+        coarse, (_, ax, r), (_, _, coarse_r) = self.coarse, buffers, coarser
+        if k is None:
+            status = self.lib.tfem_mg_restrict_residual(
+                _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
+                _ptr(coarse_r), self.real_bytes, coarse.n, self.n, stream)
+        else:
+            status = self.lib.tfem_mg_restrict_residual_multi(
+                _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
+                _ptr(coarse_r), self.real_bytes, coarse.n, self.n, k, stream)
+        if status:
+            _native.check(status)
+
+    def prolong_add(self, buffers, coarser, k, stream):
+        """x += m P (x of the level below)."""
+        coarse, (x, _, _), (coarse_x, _, _) = self.coarse, buffers, coarser
+        if k is None:
+            status = self.lib.tfem_mg_prolong_add(_ptr(self.parents), _ptr(self.mask), _ptr(coarse_x), _ptr(x),
+                                                  self.real_bytes, self.n, coarse.n, stream)
+        else:
+            status = self.lib.tfem_mg_prolong_add_multi(_ptr(self.parents), _ptr(self.mask), _ptr(coarse_x), _ptr(x),
+                                                        self.real_bytes, self.n, coarse.n, k, stream)
+        if status:
+            _native.check(status)
+
     def __repr__(self):
         extra = ", renumbered by the engine" if self.engine.renumbered else ""
         return f"<multigrid level: {self.n} DoFs, {self.op}{extra}>"
 
 
-class GeometricMultigrid:
+class _P2Level(_Level):
+    """The P2 space on the mesh of the P1 level below it.  P is the identity on the vertex DoFs and
+    0.5 / 0.5 on an edge DoF (the P2 numbering is "vertices, then edges"); the two transfers handle
+    one vector (there are no block forms of them), the sweep is the P1 levels'.
+
+    A matrix-free P2 operator is applied in the ENGINE's numbering (the engine renumbers the edge
+    DoFs of a basis from 50,000 DoFs on; the vertex ids stay those of the P1 level): the level is
+    then ``crossing``, and its tables, mask and weights are built in that numbering."""
+
+    order = 2
+
+    def __init__(self, triangulation, basis, op):
+        super().__init__(triangulation, basis, op)
+        self.n_v = int(np.asarray(triangulation["vertices"]).shape[0])
+        self.crossing = bool(op.matrix_free and self.engine.renumbered)
+
+    def set_coarser(self, coarse, device):
+        """The transfers to and from ``coarse``, the P1 level of the same mesh: the edge table (P) and
+        its transpose (P^T), edge DoF n_v + j of a crossing level being the caller's _perm[n_v + j]."""
+        n_v = self.n_v
+        edges = np.asarray(self.triangulation["edges"]).reshape(-1, 2)
+        if self.n != n_v + edges.shape[0]:
+            raise ValueError(f"P2Multigrid: {self.n} P2 DoFs on a mesh of {n_v} vertices and {edges.shape[0]} edges")
+        if self.crossing:
+            perm = self.engine._perm.cpu().numpy()
+            if not (perm[:n_v] == np.arange(n_v)).all():
+                raise NotImplementedError("P2Multigrid: an engine that renumbers the vertex DoFs of a P2 basis")
+            edges = edges[perm[n_v:] - n_v]
+        ptr, idx = transpose_edges(edges, n_v)
+        self.coarse = coarse
+        self.edge_vertices = torch.as_tensor(np.ascontiguousarray(edges, dtype=np.int32), device=device)
+        self.pt_ptr = torch.as_tensor(ptr, device=device)
+        self.pt_idx = torch.as_tensor(idx, device=device)
+
+    def restrict_residual(self, buffers, coarser, k, stream):
+        (_, ax, r), (_, _, coarse_r) = buffers, coarser
+        status = self.lib.tfem_mg_p2_restrict_residual(
+            _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(self.coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
+            _ptr(coarse_r), self.real_bytes, self.n_v, self.n, stream)
+        if status:
+            _native.check(status)
+
+    def prolong_add(self, buffers, coarser, k, stream):
+        (x, _, _), (coarse_x, _, _) = buffers, coarser
+        status = self.lib.tfem_mg_p2_prolong_add(_ptr(self.edge_vertices), _ptr(self.mask), _ptr(coarse_x), _ptr(x),
+                                                 self.real_bytes, self.n_v, self.n, stream)
+        if status:
+            _native.check(status)
+
+
+def _build_level(name, kind, mesh, element, bilinear, layouts):
+    """The level of the class ``kind`` on ``mesh``: its ``Basis`` and the operator of ``bilinear`` in
+    the first of ``layouts`` that the basis grants.  ``name``: the hierarchy's, for the messages."""
+    basis = Basis(MeshTri(triangulation=mesh), element)
+    engine = basis._engine
+    if engine.n_fractures > 0 or engine.poly_order != kind.order:
+        raise NotImplementedError(f"{name}: a P{kind.order} basis on one triangulation is needed")
+    try:
+        expr = forms.trace(bilinear, basis, (), {})
+    except ValueError as err:
+        if str(err).startswith("coefficient:"):
+            raise NotImplementedError(f"{name}: coefficient data (basis.coefficient) has the shape of ONE mesh; "
+                                      "write the coefficient as an expression of the integration points") from err
+        raise
+    if isinstance(expr, forms.BilinearExpr) and expr.has_coefficients and expr.has_data:
+        raise NotImplementedError(f"{name}: coefficient data (basis.coefficient) has the shape of ONE mesh; write "
+                                  "the coefficient as an expression of the integration points")
+    for layout in layouts[:-1]:
+        try:
+            op = basis._bilinear_of(expr, layout)
+            break
+        except NotImplementedError:
+            pass
+    else:
+        op = basis._bilinear_of(expr, layouts[-1])
+    if not isinstance(op, FormOperator):
+        raise TypeError(f"{name}: the bilinear form did not give an operator")
+    return kind(mesh, basis, op)
+
+
+class _Hierarchy:
+    """What ``GeometricMultigrid`` and ``P2Multigrid`` share: the preparation of a level's vectors,
+    its apply, THE cycle, and ``vcycle`` / ``solve`` on one vector.  A subclass sets ``levels``
+    (coarsest first), ``nu``, ``omega``, ``dirichlet``, ``device``, ``dtype``, ``_buffers`` (per level
+    the single-vector (x, ax, r)), ``_own`` (the levels whose applies it prepares itself) and
+    ``_applies`` (stream -> the prepared applies of ``_own``)."""
+
+    #: how the refusal of a block (N, k) where one vector is expected ends
+    _BLOCKS = "blocks: vcycle_multi, solve_multi"
+
+    # ------------------------------------------------------------------ set-up
+    def _prepare_level(self, level, inward):
+        """Mask, smoothing weights and buffers of ``level`` in the numbering it runs in; ``inward``
+        takes a vector of the caller's numbering there."""
+        dev, dtype, n = self.device, self.dtype, level.n
+        level.lib = _native.load()
+        level.real_bytes = torch.empty((), dtype=dtype).element_size()
+        diag = inward(level.op.diagonal().to(dev, dtype).reshape(-1))
+        if self.dirichlet:
+            level.free = level.basis._basis_parameters["inner_dofs"].to(dev).reshape(-1).long()
+            mask = torch.zeros(n, dtype=dtype, device=dev)
+            mask[level.free] = 1
+            level.mask = inward(mask).contiguous()
+            w = level.mask / torch.where(diag != 0, diag, torch.ones_like(diag))
+        else:
+            level.free, level.mask = None, None
+            w = 1.0 / diag
+        level.w = (self.omega * w).contiguous()
+        level.x, level.ax, level.r = (torch.zeros(n, dtype=dtype, device=dev) for _ in range(3))
+
+    def _apply_of(self, level):
+        """``apply(u, out)``: out = K u on the level's buffers, in the numbering the level runs in."""
+        op = level.op
+        if op.matrix_free and (not level.engine.renumbered or level.crossing):
+            return op._rows_into()
+        if not op.matrix_free:
+            csr = op.to_csr().to(self.device)
+            if csr.perm is None:
+                return _into(csr._prepared_spmv)
+
+        def through_matvec(u, out):
+            out.copy_(op.matvec(u))
+
+        return through_matvec
+
+    def _level_applies(self):
+        """The applies of ``levels`` prepared for the current stream (those of ``_own`` are kept here)."""
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        applies = self._applies.get(key)
+        if applies is None:
+            applies = self._applies[key] = [self._apply_of(level) for level in self._own]
+        return applies
+
+    # ------------------------------------------------------------------ the cycle
+    def _cycle(self, l, buffers, k, applies, stream):
+        """r of level l -> x of level l on ``buffers``, per level (x, K x, r): vectors (k None) or
+        (n_l, k) blocks.  The coarsest level is one dense product."""
+        level, mine = self.levels[l], buffers[l]
+        x, ax, r = mine
+        if l == 0:
+            if k is None:
+                torch.mv(level.inverse, r, out=x)
+            else:
+                torch.mm(level.inverse, r, out=x)
+            return
+        coarser, apply = buffers[l - 1], applies[l]
+        level.smooth(mine, k, True, stream)
+        for _ in range(self.nu - 1):
+            apply(x, ax)
+            level.smooth(mine, k, False, stream)
+        apply(x, ax)
+        level.restrict_residual(mine, coarser, k, stream)
+        self._cycle(l - 1, buffers, k, applies, stream)
+        level.prolong_add(mine, coarser, k, stream)
+        for _ in range(self.nu):
+            apply(x, ax)
+            level.smooth(mine, k, False, stream)
+
+    def _vector(self, v, what):
+        """``v`` as a flat vector of the hierarchy's type in the numbering of the finest level."""
+        name, top = type(self).__name__, self.levels[-1]
+        if _is_block(v):
+            raise NotImplementedError(f"{name}.{what}: blocks (N, k) of vectors; one vector (N,) or (N, 1) "
+                                      f"({self._BLOCKS})")
+        flat = v.detach().to(self.device, self.dtype).reshape(-1)
+        if flat.shape[0] != top.n:
+            raise ValueError(f"{name}.{what}: {flat.shape[0]} entries, the finest level has {top.n} DoFs")
+        return top.engine._dofs_in(flat) if top.crossing else flat
+
+    def _result(self, x, like):
+        top = self.levels[-1]
+        if top.crossing:
+            x = top.engine._dofs_out(x)
+        return top.engine._home(x).reshape(like.shape)
+
+    def _vcycle_into(self, r):
+        """The cycle on the single-vector buffers, r in the finest level's numbering; returns the
+        buffer that holds the result (valid until the next cycle)."""
+        top = self.levels[-1]
+        top.r.copy_(r)
+        self._cycle(len(self.levels) - 1, self._buffers, None, self._level_applies(),
+                    _native.current_stream(self.device))
+        return top.x
+
+    def vcycle(self, r):
+        """One V-cycle on the residual ``r`` ((N,) or (N, 1), the DoFs of ``basis``): the approximate
+        solution z of K z = r on the free DoFs, 0 on the held ones; shaped like r."""
+        flat = self._vector(r, "vcycle")
+        with torch.cuda.device(self.device):
+            z = self._vcycle_into(flat).clone()
+        return self._result(z, r)
+
+    def solve(self, b, x0=None, rtol=1e-10, maxiter=100, free=None):
+        """Conjugate gradients preconditioned by ``vcycle`` for K x = b on the free DoFs (the held
+        ones keep x0's values, 0 by default).  The relative residual |r| / |m b| is checked every
+        iteration.  Returns (x shaped like b, iterations, relative residual)."""
+        if free is not None:
+            raise NotImplementedError(f"{type(self).__name__}.solve: a custom set of free DoFs; the hierarchy holds "
+                                      "the boundary DoFs of every level (dirichlet=True) or none")
+        rhs = self._vector(b, "solve")
+        start = None if x0 is None else self._vector(x0, "solve")
+        with torch.cuda.device(self.device):
+            x, it, res = _cycle_pcg(self._level_applies()[-1], self._vcycle_into, self.levels[-1].mask, rhs, start,
+                                    rtol, maxiter)
+        return self._result(x, b), it, res
+
+
+class GeometricMultigrid(_Hierarchy):
     """V(nu, nu)-cycle and multigrid-preconditioned CG for a P1 form on ``levels`` uniform
     refinements of ``coarse_triangulation`` (a triangle-format dictionary, ``meshgen``).
 
@@ -129,8 +400,9 @@ class GeometricMultigrid:
     ``engine``, ``n``), ``parents`` the parent tables of the refinements (``parents[l - 1]`` takes
     level l - 1 to level l).
 
-    Blocks (N, k) of right-hand sides go through ``vcycle_multi`` and ``solve_multi``: the same
-    number of launches per cycle whatever k is.  ``vcycle`` and ``solve`` take one vector.
+    ``vcycle`` and ``solve`` take one vector.  Blocks (N, k) of right-hand sides go through
+    ``vcycle_multi`` and ``solve_multi``: the same cycle on (n_l, k) buffers, so the same number of
+    launches whatever k is.
 
     Refused with NotImplementedError: P2 elements (``P2Multigrid``), fracture bases, coefficient data
     (``basis.coefficient``: its shape belongs to one mesh), a custom set of free DoFs; and a coarse
@@ -172,63 +444,25 @@ class GeometricMultigrid:
         try:
             if element is None:  # built here: an element keeps tables in the default dtype of its creation
                 element = ElementTri(polynomial_order=1, integration_order=int(quadrature_order))
-            self.levels = [self._build_level(mesh, element, bilinear) for mesh in meshes]
+            self.levels = [_build_level("GeometricMultigrid", _Level, mesh, element, bilinear, ("operator",))
+                           for mesh in meshes]
         finally:
             torch.set_default_dtype(previous)
         self.basis = self.levels[-1].basis
         self.operator = self.levels[-1].op
         self.device, self.dtype = self.levels[-1].engine.device, self.levels[-1].engine.dtype
-        self._lib = _native.load()
-        self._real_bytes = torch.empty((), dtype=self.dtype).element_size()
         with torch.cuda.device(self.device):
             for l, level in enumerate(self.levels):
-                self._prepare_level(level, None if l == 0 else self.parents[l - 1],
-                                    None if l == 0 else self.levels[l - 1].n)
+                self._prepare_level(level, _identity)
+                if l > 0:
+                    level.set_coarser(self.levels[l - 1], self.parents[l - 1], self.device)
             self._factor_coarse(self.levels[0])
+        self._own = self.levels
+        self._buffers = [(level.x, level.ax, level.r) for level in self.levels]
         self._applies = {}  # stream -> the prepared applies of the levels
         self._blocks = {}  # k -> per level (x, ax, r) of shape (n_l, k); insertion order = age of last use
 
     # ------------------------------------------------------------------ set-up
-    def _build_level(self, mesh, element, bilinear):
-        basis = Basis(MeshTri(triangulation=mesh), element)
-        engine = basis._engine
-        if engine.n_fractures > 0 or engine.poly_order != 1:
-            raise NotImplementedError("GeometricMultigrid: a P1 basis on one triangulation is needed")
-        try:
-            expr = forms.trace(bilinear, basis, (), {})
-        except ValueError as err:
-            if str(err).startswith("coefficient:"):
-                raise NotImplementedError("GeometricMultigrid: coefficient data (basis.coefficient) has the shape "
-                                          "of ONE mesh; write the coefficient as an expression of the "
-                                          "integration points") from err
-            raise
-        if isinstance(expr, forms.BilinearExpr) and expr.has_coefficients and expr.has_data:
-            raise NotImplementedError("GeometricMultigrid: coefficient data (basis.coefficient) has the shape of ONE "
-                                      "mesh; write the coefficient as an expression of the integration points")
-        op = basis._bilinear_of(expr, "operator")
-        if not isinstance(op, FormOperator):
-            raise TypeError("GeometricMultigrid: the bilinear form did not give an operator")
-        return _Level(mesh, basis, op)
-
-    def _prepare_level(self, level, parents, n_coarse):
-        dev, dtype, n = self.device, self.dtype, level.n
-        diag = level.op.diagonal().to(dev, dtype).reshape(-1)
-        if self.dirichlet:
-            level.free = level.basis._basis_parameters["inner_dofs"].to(dev).reshape(-1).long()
-            level.mask = torch.zeros(n, dtype=dtype, device=dev)
-            level.mask[level.free] = 1
-            w = level.mask / torch.where(diag != 0, diag, torch.ones_like(diag))
-        else:
-            level.free, level.mask = None, None
-            w = 1.0 / diag
-        level.w = (self.omega * w).contiguous()
-        level.x, level.ax, level.r = (torch.zeros(n, dtype=dtype, device=dev) for _ in range(3))
-        if parents is not None:
-            ptr, idx = transpose_parents(parents, n_coarse)
-            level.parents = torch.as_tensor(np.ascontiguousarray(parents, dtype=np.int32), device=dev)
-            level.pt_ptr = torch.as_tensor(ptr, device=dev)
-            level.pt_idx = torch.as_tensor(idx, device=dev)
-
     def _factor_coarse(self, level):
         n_free = level.n if level.free is None else int(level.free.numel())
         if n_free > Basis.DENSE_SOLVE_LIMIT:
@@ -256,102 +490,6 @@ class GeometricMultigrid:
             else:
                 level.inverse[level.free[:, None], level.free[None, :]] = inverse
 
-    def _apply_of(self, level):
-        """``apply(u, out)``: out = K u on the level's buffers, vectors in the caller's numbering."""
-        op, engine = level.op, level.engine
-        if op.matrix_free and not engine.renumbered:
-            return op._rows_into()
-        if not op.matrix_free:
-            csr = op.to_csr().to(self.device)
-            if csr.perm is None:
-                return _into(csr._prepared_spmv)
-
-        def through_matvec(u, out):
-            out.copy_(op.matvec(u))
-
-        return through_matvec
-
-    def _level_applies(self):
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        applies = self._applies.get(key)
-        if applies is None:
-            applies = self._applies[key] = [self._apply_of(level) for level in self.levels]
-        return applies
-
-    # ------------------------------------------------------------------ the cycle
-    def _smooth(self, level, first, stream):
-        status = self._lib.tfem_mg_smooth(_native.ptr(level.x), _native.ptr(level.r),
-                                          None if first else _native.ptr(level.ax), _native.ptr(level.w),
-                                          self._real_bytes, level.n, 1 if first else 0, stream)
-        if status:
-            _native.check(status)
-
-    def _cycle(self, l, applies, stream):
-        level = self.levels[l]
-        if l == 0:
-            torch.mv(level.inverse, level.r, out=level.x)
-            return
-        coarse, apply, lib = self.levels[l - 1], applies[l], self._lib
-        self._smooth(level, True, stream)
-        for _ in range(self.nu - 1):
-            apply(level.x, level.ax)
-            self._smooth(level, False, stream)
-        apply(level.x, level.ax)
-        status = lib.tfem_mg_restrict_residual(
-            _native.ptr(level.pt_ptr), _native.ptr(level.pt_idx), _native.ptr(coarse.mask), _native.ptr(level.mask),
-            _native.ptr(level.r), _native.ptr(level.ax), _native.ptr(coarse.r), self._real_bytes, coarse.n, level.n,
-            stream)
-        if status:
-            _native.check(status)
-        self._cycle(l - 1, applies, stream)
-        status = lib.tfem_mg_prolong_add(_native.ptr(level.parents), _native.ptr(level.mask), _native.ptr(coarse.x),
-                                         _native.ptr(level.x), self._real_bytes, level.n, coarse.n, stream)
-        if status:
-            _native.check(status)
-        for _ in range(self.nu):
-            apply(level.x, level.ax)
-            self._smooth(level, False, stream)
-
-    def _vector(self, v, what):
-        if _is_block(v):
-            raise NotImplementedError(f"GeometricMultigrid.{what}: blocks (N, k) of vectors; one vector (N,) or (N, 1) "
-                                      f"(blocks: vcycle_multi, solve_multi)")
-        flat = v.detach().to(self.device, self.dtype).reshape(-1)
-        if flat.shape[0] != self.levels[-1].n:
-            raise ValueError(f"GeometricMultigrid.{what}: {flat.shape[0]} entries, the finest level has "
-                             f"{self.levels[-1].n} DoFs")
-        return flat
-
-    def _vcycle_into(self, r):
-        """The cycle on the finest level's buffers; returns the buffer that holds the result (valid
-        until the next cycle)."""
-        top = self.levels[-1]
-        top.r.copy_(r)
-        self._cycle(len(self.levels) - 1, self._level_applies(), _native.current_stream(self.device))
-        return top.x
-
-    def vcycle(self, r):
-        """One V-cycle on the residual ``r`` ((N,) or (N, 1), the finest level's DoFs): the
-        approximate solution z of K z = r on the free DoFs, 0 on the held ones; shaped like r."""
-        flat = self._vector(r, "vcycle")
-        with torch.cuda.device(self.device):
-            z = self._vcycle_into(flat).clone()
-        return self.levels[-1].engine._home(z).reshape(r.shape)
-
-    def solve(self, b, x0=None, rtol=1e-10, maxiter=100, free=None):
-        """Conjugate gradients preconditioned by ``vcycle`` for K x = b on the free DoFs (the held
-        ones keep x0's values, 0 by default).  The relative residual |r| / |m b| is checked every
-        iteration.  Returns (x shaped like b, iterations, relative residual)."""
-        if free is not None:
-            raise NotImplementedError("GeometricMultigrid.solve: a custom set of free DoFs; the hierarchy holds the "
-                                      "boundary DoFs of every level (dirichlet=True) or none")
-        top = self.levels[-1]
-        rhs = self._vector(b, "solve")
-        with torch.cuda.device(self.device):
-            x, it, res = _cycle_pcg(self._level_applies()[-1], self._vcycle_into, top.mask, rhs,
-                                    None if x0 is None else self._vector(x0, "solve"), rtol, maxiter)
-        return top.engine._home(x).reshape(b.shape), it, res
-
     # ------------------------------------------------------------------ blocks of right-hand sides
     def _block_buffers(self, k):
         """Per level (x, ax, r) of shape (n_l, k), zero on first use of the width k and reused; the
@@ -370,42 +508,6 @@ class GeometricMultigrid:
         self._blocks[k] = buffers  # the youngest
         return buffers
 
-    def _smooth_multi(self, level, buffers, k, first, stream):
-        x, ax, r = buffers
-        status = self._lib.tfem_mg_smooth_multi(_native.ptr(x), _native.ptr(r), None if first else _native.ptr(ax),
-                                                _native.ptr(level.w), self._real_bytes, level.n, k,
-                                                1 if first else 0, stream)
-        if status:
-            _native.check(status)
-
-    def _cycle_multi(self, l, buffers, k, applies, stream):
-        """``_cycle`` on the block buffers of the width k: r of level l -> x of level l."""
-        level, (x, ax, r) = self.levels[l], buffers[l]
-        if l == 0:
-            torch.mm(level.inverse, r, out=x)
-            return
-        coarse, apply, lib = self.levels[l - 1], applies[l], self._lib
-        coarse_x, _, coarse_r = buffers[l - 1]
-        self._smooth_multi(level, buffers[l], k, True, stream)
-        for _ in range(self.nu - 1):
-            apply(x, ax)
-            self._smooth_multi(level, buffers[l], k, False, stream)
-        apply(x, ax)
-        status = lib.tfem_mg_restrict_residual_multi(
-            _native.ptr(level.pt_ptr), _native.ptr(level.pt_idx), _native.ptr(coarse.mask), _native.ptr(level.mask),
-            _native.ptr(r), _native.ptr(ax), _native.ptr(coarse_r), self._real_bytes, coarse.n, level.n, k, stream)
-        if status:
-            _native.check(status)
-        self._cycle_multi(l - 1, buffers, k, applies, stream)
-        status = lib.tfem_mg_prolong_add_multi(_native.ptr(level.parents), _native.ptr(level.mask),
-                                               _native.ptr(coarse_x), _native.ptr(x), self._real_bytes, level.n,
-                                               coarse.n, k, stream)
-        if status:
-            _native.check(status)
-        for _ in range(self.nu):
-            apply(x, ax)
-            self._smooth_multi(level, buffers[l], k, False, stream)
-
     def _block(self, V, what):
         if V.dim() != 2 or V.shape[0] != self.levels[-1].n or V.shape[1] < 1:
             raise ValueError(f"GeometricMultigrid.{what}: a block of shape ({self.levels[-1].n}, k) with k >= 1, "
@@ -419,14 +521,14 @@ class GeometricMultigrid:
         buffers = self._block_buffers(k)
         top = len(self.levels) - 1
         buffers[top][2].copy_(R)
-        self._cycle_multi(top, buffers, k, self._level_applies(), _native.current_stream(self.device))
+        self._cycle(top, buffers, k, self._level_applies(), _native.current_stream(self.device))
         return buffers[top][0]
 
     def vcycle_multi(self, R):
         """One V-cycle on every column of ``R`` (N, k), k >= 1: Z (N, k) with column j the approximate
-        solution of K z = r_j on the free DoFs, 0 on the held ones.  The launches of ``vcycle``, each
-        on (n_l, k) row-major blocks: the block applies of the levels, the tfem_mg_*_multi kernels,
-        and one dense product on the coarsest level.  The block buffers are separate from those of
+        solution of K z = r_j on the free DoFs, 0 on the held ones.  The cycle of ``vcycle``, every
+        launch on (n_l, k) row-major blocks: the block applies of the levels, the block kernels of
+        csrc/tfem_mg_multi.hip, and one dense product on the coarsest level.  The block buffers are separate from those of
         ``vcycle`` and kept for the ``BLOCK_WIDTHS_KEPT`` most recently used widths."""
         block = self._block(R, "vcycle_multi")
         with torch.cuda.device(self.device):
@@ -516,20 +618,16 @@ class GeometricMultigrid:
                 f"omega={self.omega:.3g}, dtype={self.dtype})")
 
 
-class P2Multigrid:
+class P2Multigrid(_Hierarchy):
     """V(nu, nu)-cycle and multigrid-preconditioned CG for a P2 form: a P2 level on the finest mesh
     of a P1 hierarchy (p-coarsening first, then the h-hierarchy of ``GeometricMultigrid``).
 
     P1 is a subspace of P2 on one mesh and both spaces are discretised from the same callable, so
     the P1 operator of the finest mesh IS the Galerkin operator P^T K2 P of the P2 one: no triple
-    product here either.  P is the identity on the vertex DoFs and 0.5 / 0.5 on an edge DoF (the
-    P2 numbering is "vertices, then edges"); the two transfers are csrc/tfem_mg_p2.hip.
-
-        x = w r;  (nu - 1) x  x += w (r - K x)                  w = omega * m2 / diag K2
-        r1 = m1 P^T( m2 (r - K x) )                              tfem_mg_p2_restrict_residual
-        e1 = the P1 V-cycle of r1                                GeometricMultigrid, its own buffers
-        x += m2 P e1                                             tfem_mg_p2_prolong_add
-        nu x  x += w (r - K x)                                   tfem_mg_smooth
+    product here either.  The cycle is the one of ``GeometricMultigrid`` run over ``levels``, the P1
+    levels and then the P2 level: the P2 level sweeps with w = omega * m2 / diag K2 and makes its own
+    two transfers (csrc/tfem_mg_p2.hip), and below it the cycle runs on the P1 hierarchy's own
+    buffers with the P1 hierarchy's own prepared applies.
 
     The arguments are those of ``GeometricMultigrid`` (``levels`` refinements below the mesh that
     carries the P2 level, 0 allowed; ``quadrature_order`` of both elements).  ``p1`` is the P1
@@ -545,167 +643,37 @@ class P2Multigrid:
     Refused with NotImplementedError: what ``GeometricMultigrid`` refuses, blocks (N, k) of vectors
     (``vcycle_multi`` / ``solve_multi`` are not built for P2) and a custom set of free DoFs."""
 
+    _BLOCKS = "vcycle_multi and solve_multi are not built for P2"
+
     def __init__(self, coarse_triangulation, levels, bilinear, quadrature_order=3, dirichlet=True, nu=2,
                  omega=2.0 / 3.0, dtype=None):
         self.p1 = GeometricMultigrid(coarse_triangulation, levels, bilinear, quadrature_order, dirichlet, nu, omega,
                                      dtype)
         self.nu, self.omega, self.dirichlet = self.p1.nu, self.p1.omega, self.p1.dirichlet
         self.device, self.dtype = self.p1.device, self.p1.dtype
-        self._lib, self._real_bytes = self.p1._lib, self.p1._real_bytes
-        mesh = self.p1.levels[-1].triangulation
         previous = torch.get_default_dtype()
         torch.set_default_dtype(self.dtype)
         try:  # an element keeps tables in the default dtype of its creation
             element = ElementTri(polynomial_order=2, integration_order=int(quadrature_order))
-            top = self._build_level(mesh, element, bilinear)
+            top = _build_level("P2Multigrid", _P2Level, self.p1.levels[-1].triangulation, element, bilinear,
+                               ("matrix_free", "operator"))
         finally:
             torch.set_default_dtype(previous)
         self.basis, self.operator = top.basis, top.op
         self.levels = self.p1.levels + [top]
         with torch.cuda.device(self.device):
-            self._prepare_level(top, mesh)
+            top.set_coarser(self.p1.levels[-1], self.device)
+            self._prepare_level(top, top.engine._dofs_in if top.crossing else _identity)
+        self._own = [top]
+        self._buffers = self.p1._buffers + [(top.x, top.ax, top.r)]
         self._applies = {}  # stream -> the prepared apply of the P2 level
 
-    # ------------------------------------------------------------------ set-up
-    @staticmethod
-    def _build_level(mesh, element, bilinear):
-        basis = Basis(MeshTri(triangulation=mesh), element)
-        expr = forms.trace(bilinear, basis, (), {})
-        try:
-            op = basis._bilinear_of(expr, "matrix_free")
-        except NotImplementedError:
-            op = basis._bilinear_of(expr, "operator")
-        if not isinstance(op, FormOperator):
-            raise TypeError("P2Multigrid: the bilinear form did not give an operator")
-        return _Level(mesh, basis, op)
-
-    def _prepare_level(self, level, mesh):
-        dev, dtype, n, engine = self.device, self.dtype, level.n, level.engine
-        n_v = int(np.asarray(mesh["vertices"]).shape[0])
-        edges = np.asarray(mesh["edges"]).reshape(-1, 2)
-        if n != n_v + edges.shape[0]:
-            raise ValueError(f"P2Multigrid: {n} P2 DoFs on a mesh of {n_v} vertices and {edges.shape[0]} edges")
-        level.n_v = n_v
-        # the numbering the level runs in: the engine's for the matrix-free launch (vertex ids are the
-        # caller's, edge DoF n_v + j of the engine is the caller's _perm[n_v + j]), the caller's otherwise
-        level.crossing = bool(level.op.matrix_free and engine.renumbered)
-        inward = engine._dofs_in if level.crossing else (lambda v: v)
-        if level.crossing:
-            perm = engine._perm.cpu().numpy()
-            if not (perm[:n_v] == np.arange(n_v)).all():
-                raise NotImplementedError("P2Multigrid: an engine that renumbers the vertex DoFs of a P2 basis")
-            edges = edges[perm[n_v:] - n_v]
-        diag = inward(level.op.diagonal().to(dev, dtype).reshape(-1))
-        if self.dirichlet:
-            level.free = level.basis._basis_parameters["inner_dofs"].to(dev).reshape(-1).long()
-            mask = torch.zeros(n, dtype=dtype, device=dev)
-            mask[level.free] = 1
-            level.mask = inward(mask).contiguous()
-            w = level.mask / torch.where(diag != 0, diag, torch.ones_like(diag))
-        else:
-            level.free, level.mask = None, None
-            w = 1.0 / diag
-        level.w = (self.omega * w).contiguous()
-        level.x, level.ax, level.r = (torch.zeros(n, dtype=dtype, device=dev) for _ in range(3))
-        ptr, idx = transpose_edges(edges, n_v)
-        level.edge_vertices = torch.as_tensor(np.ascontiguousarray(edges, dtype=np.int32), device=dev)
-        level.pt_ptr = torch.as_tensor(ptr, device=dev)
-        level.pt_idx = torch.as_tensor(idx, device=dev)
-
-    def _apply_of(self, level):
-        """``apply(u, out)``: out = K2 u on the level's buffers, in the numbering of the level."""
-        op = level.op
-        if op.matrix_free:
-            return op._rows_into()
-        csr = op.to_csr().to(self.device)
-        if csr.perm is None:
-            return _into(csr._prepared_spmv)
-
-        def through_matvec(u, out):
-            out.copy_(op.matvec(u))
-
-        return through_matvec
-
-    def _top_apply(self):
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        apply = self._applies.get(key)
-        if apply is None:
-            apply = self._applies[key] = self._apply_of(self.levels[-1])
-        return apply
-
-    # ------------------------------------------------------------------ the cycle
-    def _cycle(self, apply, stream):
-        level, coarse, lib, smooth = self.levels[-1], self.p1.levels[-1], self._lib, self.p1._smooth
-        smooth(level, True, stream)
-        for _ in range(self.nu - 1):
-            apply(level.x, level.ax)
-            smooth(level, False, stream)
-        apply(level.x, level.ax)
-        status = lib.tfem_mg_p2_restrict_residual(
-            _native.ptr(level.pt_ptr), _native.ptr(level.pt_idx), _native.ptr(coarse.mask), _native.ptr(level.mask),
-            _native.ptr(level.r), _native.ptr(level.ax), _native.ptr(coarse.r), self._real_bytes, level.n_v, level.n,
-            stream)
-        if status:
-            _native.check(status)
-        self.p1._cycle(len(self.p1.levels) - 1, self.p1._level_applies(), stream)
-        status = lib.tfem_mg_p2_prolong_add(_native.ptr(level.edge_vertices), _native.ptr(level.mask),
-                                            _native.ptr(coarse.x), _native.ptr(level.x), self._real_bytes, level.n_v,
-                                            level.n, stream)
-        if status:
-            _native.check(status)
-        for _ in range(self.nu):
-            apply(level.x, level.ax)
-            smooth(level, False, stream)
-
-    def _vector(self, v, what):
-        """``v`` as a flat vector of the hierarchy's type in the numbering of the P2 level."""
-        top = self.levels[-1]
-        if _is_block(v):
-            raise NotImplementedError(f"P2Multigrid.{what}: blocks (N, k) of vectors; one vector (N,) or (N, 1) "
-                                      f"(vcycle_multi and solve_multi are not built for P2)")
-        flat = v.detach().to(self.device, self.dtype).reshape(-1)
-        if flat.shape[0] != top.n:
-            raise ValueError(f"P2Multigrid.{what}: {flat.shape[0]} entries, the P2 level has {top.n} DoFs")
-        return top.engine._dofs_in(flat) if top.crossing else flat
-
-    def _result(self, x, like):
-        top = self.levels[-1]
-        if top.crossing:
-            x = top.engine._dofs_out(x)
-        return top.engine._home(x).reshape(like.shape)
-
-    def _vcycle_into(self, r):
-        """The cycle on the P2 level's buffers, r in the level's numbering; returns the buffer that
-        holds the result (valid until the next cycle)."""
-        top = self.levels[-1]
-        top.r.copy_(r)
-        self._cycle(self._top_apply(), _native.current_stream(self.device))
-        return top.x
-
-    def vcycle(self, r):
-        """One V-cycle on the residual ``r`` ((N,) or (N, 1), the DoFs of ``basis``): the approximate
-        solution z of K z = r on the free DoFs, 0 on the held ones; shaped like r."""
-        flat = self._vector(r, "vcycle")
-        with torch.cuda.device(self.device):
-            z = self._vcycle_into(flat).clone()
-        return self._result(z, r)
-
-    def solve(self, b, x0=None, rtol=1e-10, maxiter=100, free=None):
-        """Conjugate gradients preconditioned by ``vcycle`` for K x = b on the free DoFs: the contract
-        and the recurrence of ``GeometricMultigrid.solve`` (the held DoFs keep x0's values, 0 by
-        default; |r| / |m b| is checked every iteration).  Returns (x shaped like b, iterations,
-        relative residual)."""
-        if free is not None:
-            raise NotImplementedError("P2Multigrid.solve: a custom set of free DoFs; the hierarchy holds the boundary "
-                                      "DoFs of every level (dirichlet=True) or none")
-        rhs = self._vector(b, "solve")
-        start = None if x0 is None else self._vector(x0, "solve")
-        with torch.cuda.device(self.device):
-            x, it, res = _cycle_pcg(self._top_apply(), self._vcycle_into, self.levels[-1].mask, rhs, start, rtol,
-                                    maxiter)
-        return self._result(x, b), it, res
+    def _level_applies(self):
+        return self.p1._level_applies() + super()._level_applies()
 
     def __repr__(self):
         sizes = ", ".join(str(level.n) for level in self.levels)
         return (f"P2Multigrid(P2 over {len(self.p1.levels) - 1} refinements: {sizes} DoFs, V({self.nu},{self.nu}), "
                 f"omega={self.omega:.3g}, dtype={self.dtype})")
+
+

@@ -40,33 +40,34 @@ def timed(fn, reps=1):
     return (time.perf_counter() - t0) / reps, out
 
 
-def cycle_parts(mg, reps):
-    """Seconds per cycle of (operator launches, tfem_mg launches, coarse solve), each class alone."""
+def cycle_parts(mg, reps, k=None, bottom=1):
+    """Seconds per cycle of (operator launches, tfem_mg launches, what lies below), each class alone:
+    the launches of the levels from ``bottom`` up on the single-vector buffers (k None) or the block
+    buffers of the width k, and the cycle of the level under ``bottom`` (the coarse solve for 1)."""
+    buffers = mg._buffers if k is None else mg._block_buffers(k)
     applies = mg._level_applies()
     stream = _native.current_stream(mg.device)
-    pairs = list(zip(mg.levels[1:], mg.levels[:-1], applies[1:]))
+    tops = range(bottom, len(mg.levels))
 
     def operators():
-        for level, _, apply in pairs:
+        for l in tops:
+            x, ax, _ = buffers[l]
             for _ in range(2 * mg.nu):
-                apply(level.x, level.ax)
+                applies[l](x, ax)
 
     def transfers():
-        for level, coarse, _ in pairs:
-            mg._smooth(level, True, stream)
+        for l in tops:
+            level = mg.levels[l]
+            level.smooth(buffers[l], k, True, stream)
             for _ in range(2 * mg.nu - 1):
-                mg._smooth(level, False, stream)
-            mg._lib.tfem_mg_restrict_residual(
-                _native.ptr(level.pt_ptr), _native.ptr(level.pt_idx), _native.ptr(coarse.mask), _native.ptr(level.mask),
-                _native.ptr(level.r), _native.ptr(level.ax), _native.ptr(coarse.r), mg._real_bytes, coarse.n, level.n,
-                stream)
-            mg._lib.tfem_mg_prolong_add(_native.ptr(level.parents), _native.ptr(level.mask), _native.ptr(coarse.x),
-                                        _native.ptr(level.x), mg._real_bytes, level.n, coarse.n, stream)
+                level.smooth(buffers[l], k, False, stream)
+            level.restrict_residual(buffers[l], buffers[l - 1], k, stream)
+            level.prolong_add(buffers[l], buffers[l - 1], k, stream)
 
-    def coarse_solve():
-        mg._cycle(0, applies, stream)
+    def below():
+        mg._cycle(bottom - 1, buffers, k, applies, stream)
 
-    return tuple(timed(fn, reps)[0] for fn in (operators, transfers, coarse_solve))
+    return tuple(timed(fn, reps)[0] for fn in (operators, transfers, below))
 
 
 def main():

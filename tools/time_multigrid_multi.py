@@ -19,45 +19,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pytorch_fem_solver_amd import GeometricMultigrid, _native, meshgen  # noqa: E402
+from pytorch_fem_solver_amd import GeometricMultigrid, meshgen  # noqa: E402
 from time_multigrid import cycle_parts, load, stiffness, timed  # noqa: E402
 
 SCALES = (1.0, -2.0, 0.5, 3.0, -0.25, 1.5, -4.0, 0.75)
-
-
-def block_cycle_parts(mg, k, reps):
-    """Seconds per block cycle of (operator launches, tfem_mg_*_multi launches, coarse product), each
-    class alone on the block buffers of the width k."""
-    buffers = mg._block_buffers(k)
-    applies = mg._level_applies()
-    stream = _native.current_stream(mg.device)
-    tops = range(1, len(mg.levels))
-
-    def operators():
-        for l in tops:
-            x, ax, _ = buffers[l]
-            for _ in range(2 * mg.nu):
-                applies[l](x, ax)
-
-    def transfers():
-        for l in tops:
-            level, coarse = mg.levels[l], mg.levels[l - 1]
-            x, ax, r = buffers[l]
-            mg._smooth_multi(level, buffers[l], k, True, stream)
-            for _ in range(2 * mg.nu - 1):
-                mg._smooth_multi(level, buffers[l], k, False, stream)
-            mg._lib.tfem_mg_restrict_residual_multi(
-                _native.ptr(level.pt_ptr), _native.ptr(level.pt_idx), _native.ptr(coarse.mask), _native.ptr(level.mask),
-                _native.ptr(r), _native.ptr(ax), _native.ptr(buffers[l - 1][2]), mg._real_bytes, coarse.n, level.n, k,
-                stream)
-            mg._lib.tfem_mg_prolong_add_multi(_native.ptr(level.parents), _native.ptr(level.mask),
-                                              _native.ptr(buffers[l - 1][0]), _native.ptr(x), mg._real_bytes, level.n,
-                                              coarse.n, k, stream)
-
-    def coarse_product():
-        mg._cycle_multi(0, buffers, k, applies, stream)
-
-    return tuple(timed(fn, reps)[0] for fn in (operators, transfers, coarse_product))
 
 
 def spread(values):
@@ -128,7 +93,7 @@ def main():
         mg._vcycle_multi_into(R)
         t_block, _ = timed(lambda: mg._vcycle_multi_into(R), reps)
         print(f"one block cycle, k = {k}: {t_block * 1e3:.3f} ms = {t_block / t_single:.2f} single cycles "
-              f"({t_block / k * 1e3:.3f} ms per column); alone: {parts_text(block_cycle_parts(mg, k, reps))}")
+              f"({t_block / k * 1e3:.3f} ms per column); alone: {parts_text(cycle_parts(mg, reps, k))}")
         top = len(mg.levels) - 1
         x, ax, _ = mg._block_buffers(k)[top]
         t_top, _ = timed(lambda: mg._level_applies()[-1](x, ax), reps)

@@ -12,61 +12,17 @@ on its own, back to back, in the numbers one cycle issues them (2 nu applies and
 restriction, one prolongation, one P1 cycle).  Wall time around a synchronised device.  What is
 printed is also written to --log (default profiles/p2_multigrid.log, appended)."""
 import argparse
-import math
 import os
 import statistics
 import sys
-import time
 
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-from pytorch_fem_solver_amd import P2Multigrid, _native, meshgen  # noqa: E402
-
-
-def stiffness(b):
-    return b.v_grad @ b.v_grad.mT
-
-
-def load(b):
-    x, y = torch.split(b.integration_points, 1, dim=-1)
-    return 2.0 * math.pi**2 * torch.sin(math.pi * x) * torch.sin(math.pi * y) * b.v
-
-
-def timed(fn, reps=1):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / reps, out
-
-
-def cycle_parts(mg, reps):
-    """Seconds per cycle of (P2 operator launches, tfem_mg launches of the P2 level, the P1 cycle),
-    each class alone."""
-    apply, stream = mg._top_apply(), _native.current_stream(mg.device)
-    top, coarse, p1 = mg.levels[-1], mg.p1.levels[-1], mg.p1
-
-    def operators():
-        for _ in range(2 * mg.nu):
-            apply(top.x, top.ax)
-
-    def transfers():
-        p1._smooth(top, True, stream)
-        for _ in range(2 * mg.nu - 1):
-            p1._smooth(top, False, stream)
-        mg._lib.tfem_mg_p2_restrict_residual(
-            _native.ptr(top.pt_ptr), _native.ptr(top.pt_idx), _native.ptr(coarse.mask), _native.ptr(top.mask),
-            _native.ptr(top.r), _native.ptr(top.ax), _native.ptr(coarse.r), mg._real_bytes, top.n_v, top.n, stream)
-        mg._lib.tfem_mg_p2_prolong_add(_native.ptr(top.edge_vertices), _native.ptr(top.mask), _native.ptr(coarse.x),
-                                       _native.ptr(top.x), mg._real_bytes, top.n_v, top.n, stream)
-
-    def p1_cycle():
-        p1._cycle(len(p1.levels) - 1, p1._level_applies(), stream)
-
-    return tuple(timed(fn, reps)[0] for fn in (operators, transfers, p1_cycle))
+from pytorch_fem_solver_amd import P2Multigrid, meshgen  # noqa: E402
+from time_multigrid import cycle_parts, load, stiffness, timed  # noqa: E402
 
 
 def main():
@@ -118,11 +74,11 @@ def main():
     reps = 20
     mg._vcycle_into(r)
     t_cycle, _ = timed(lambda: mg._vcycle_into(r), reps)
-    parts = cycle_parts(mg, reps)
+    parts = cycle_parts(mg, reps, bottom=len(mg.levels) - 1)  # the P2 level alone, the P1 cycle below it
     say(f"one V({mg.nu},{mg.nu}) cycle: {t_cycle * 1e3:.3f} ms; alone: P2 operator launches {parts[0] * 1e3:.3f} ms, "
         f"tfem_mg launches of the P2 level {parts[1] * 1e3:.3f} ms, the P1 cycle {parts[2] * 1e3:.3f} ms "
         f"(sum {sum(parts) * 1e3:.3f} ms: {', '.join(f'{100 * p / sum(parts):.0f} %' for p in parts)})")
-    t_top, _ = timed(lambda: mg._top_apply()(top.x, top.ax), reps)
+    t_top, _ = timed(lambda: mg._level_applies()[-1](top.x, top.ax), reps)
     say(f"one P2 apply: {t_top * 1e6:.1f} us")
     os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
     with open(args.log, "a") as fh:
