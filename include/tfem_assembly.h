@@ -882,6 +882,33 @@ int tfem_mg_p2_restrict_residual(const int32_t *ptr, const int32_t *idx, const v
 int tfem_mg_p2_prolong_add(const int32_t *edge_vertices, const void *mask_f, const void *e_c, void *x_f,
                            int real_bytes, int64_t n_v, int64_t n_f, void *stream);
 
+/* The same two on a block of n_vec >= 1 vectors (csrc/tfem_mg_p2_multi.hip).  b_f, ax_f, r_c, e_c,
+ * x_f are n x n_vec reals, ROW-major (the layout of tfem_mg_*_multi and tfem_p2_apply_rows_multi);
+ * the masks, ptr, idx and edge_vertices keep one entry per DoF.  One launch for any n_vec;
+ * n_vec == 1 IS the single launch above.
+ * restrict_residual: r_c[v][c] = mask_c[v] * (d(v)[c] + 0.5 * sum_p d(idx[p])[c]) with
+ *           d(j)[c] = mask_f[j] * (b_f[j][c] - ax_f[j][c]): the eight lanes per row and the order of
+ *           the single launch for every column; idx and mask_f are read once per entry, one
+ *           accumulator per column, at most 8 columns per pass.
+ * prolong_add: x_f[i][c] = x_f[i][c] + mask_f[i] * e_c[i][c] for i < n_v,
+ *           x_f[i][c] = x_f[i][c] + mask_f[i] * (0.5 * (e_c[a][c] + e_c[b][c])) for n_v <= i < n_f;
+ *           one lane per fine DoF, which reads its endpoints and mask_f once.
+ * With n_vec 2, 4 or 8 and the blocks aligned to min(16, n_vec * real_bytes) bytes the rows move
+ * in accesses of that width, otherwise value by value.  Column c of every result is bit for bit
+ * what the single launch gives for the contiguous copy of column c; no fma, no atomics, two calls
+ * give the same bits.  An entry of idx >= n_f or an endpoint >= n_v counts as 0 and touches nothing.
+ * Refusals as above, with the extents of the blocks n * n_vec * real_bytes (4 GiB or more:
+ * TFEM_ERR_INDEX_RANGE; the output overlapping an input anywhere in that extent:
+ * TFEM_ERR_INVALID_ARGUMENT), and n_vec < 1: TFEM_ERR_INVALID_ARGUMENT.  n_v == 0 succeeds and
+ * launches nothing. */
+int tfem_mg_p2_restrict_residual_multi(const int32_t *ptr, const int32_t *idx, const void *mask_c,
+                                       const void *mask_f, const void *b_f, const void *ax_f, void *r_c,
+                                       int real_bytes, int64_t n_v, int64_t n_f, int64_t n_vec,
+                                       void *stream);
+int tfem_mg_p2_prolong_add_multi(const int32_t *edge_vertices, const void *mask_f, const void *e_c,
+                                 void *x_f, int real_bytes, int64_t n_v, int64_t n_f, int64_t n_vec,
+                                 void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Interface exchange of the multi-GPU sharding (DEVICE; the path shards by element
  * range, DoFs on an inter-rank interface are summed with one all-reduce of a packed

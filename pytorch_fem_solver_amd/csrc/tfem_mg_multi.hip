@@ -39,69 +39,6 @@
 
 namespace tfem {
 
-constexpr int kMgPass = 8;  // columns per pass of the generic restriction
-
-// KE consecutive values from byte offset `byte` (a multiple of KE * sizeof(T), which is 8 or 16) of
-// a block behind a buffer resource; 0 outside it.
-template <typename T, int KE>
-__device__ __forceinline__ void mg_load_chunk(ring_rsrc_t r, unsigned byte, T (&v)[KE]) {
-  static_assert(KE * sizeof(T) == 16 || (KE == 2 && sizeof(T) == 4), "16 bytes, or two floats");
-  if constexpr (KE * sizeof(T) == 16) {
-    const ru32x4 q = __builtin_amdgcn_raw_buffer_load_b128(r, byte, 0, 0);
-    if constexpr (sizeof(T) == 8) {
-      v[0] = __builtin_bit_cast(double, ru32x2{q.x, q.y});
-      v[1] = __builtin_bit_cast(double, ru32x2{q.z, q.w});
-    } else {
-      // the words by value first: a bit_cast straight from a vector element reads element 0
-      const unsigned q0 = q.x, q1 = q.y, q2 = q.z, q3 = q.w;
-      v[0] = __builtin_bit_cast(float, q0);
-      v[1] = __builtin_bit_cast(float, q1);
-      v[2] = __builtin_bit_cast(float, q2);
-      v[3] = __builtin_bit_cast(float, q3);
-    }
-  } else {  // two dword loads: raw_buffer_load_b64 is miscompiled by this hipcc (tfem_tiles.hip)
-    v[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte, 0, 0));
-    v[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte + 4u, 0, 0));
-  }
-}
-
-template <typename T, int KE>
-__device__ __forceinline__ void mg_store_chunk(ring_rsrc_t r, unsigned byte, const T (&v)[KE]) {
-  if constexpr (KE * sizeof(T) == 16) {
-    ru32x4 q;
-    if constexpr (sizeof(T) == 8) {
-      const ru32x2 lo = __builtin_bit_cast(ru32x2, v[0]), hi = __builtin_bit_cast(ru32x2, v[1]);
-      q = ru32x4{lo.x, lo.y, hi.x, hi.y};
-    } else {
-      q = ru32x4{__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1]),
-                 __builtin_bit_cast(unsigned, v[2]), __builtin_bit_cast(unsigned, v[3])};
-    }
-    __builtin_amdgcn_raw_buffer_store_b128(q, r, byte, 0, 0);
-  } else {
-    __builtin_amdgcn_raw_buffer_store_b64(
-        ru32x2{__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1])}, r, byte, 0, 0);
-  }
-}
-
-// Row width NV in {2, 4, 8}: kE values per access, kAccesses accesses per row (SpmmShape).
-template <typename T, int NV>
-struct MgRowShape {
-  static constexpr int kE = NV * int(sizeof(T)) >= 16 ? 16 / int(sizeof(T)) : NV;
-  static constexpr int kAccesses = NV / kE;
-  static constexpr unsigned kAccessBytes = unsigned(kE * sizeof(T));
-  static constexpr unsigned kRowBytes = unsigned(NV * sizeof(T));
-};
-
-// The sum over the eight lanes of a row, the same bits in every one of them (x + y == y + x): the
-// steps of k_mg_restrict.
-template <typename T>
-__device__ __forceinline__ T mg_row_sum(T acc) {
-  acc = acc + __shfl_xor(acc, 4, 64);
-  acc = acc + __shfl_xor(acc, 2, 64);
-  acc = acc + __shfl_xor(acc, 1, 64);
-  return acc;
-}
-
 // ------------------------------------------------------------------------------------- smooth
 // total = n * n_vec values.  VEC: x, b and ax are aligned to 16 bytes; w has one entry per row and
 // is read entry by entry.
@@ -319,34 +256,6 @@ __global__ __launch_bounds__(kMgBlock) void k_mg_prolong_multi_any(const int32_t
     if (masked) v = m * v;
     mg_store<T>(r_x, i * n_vec + c, mg_load<T>(r_x, i * n_vec + c) + v);
   }
-}
-
-// ---------------------------------------------------------------------------------------- host
-
-// n * n_vec * real_bytes, or a value >= 4 GiB where that would overflow.
-static int64_t mg_block_bytes(int64_t n, int64_t n_vec, int real_bytes) {
-  const int64_t rows = n < kMgCountLimit ? n : kMgCountLimit;
-  const int64_t cols = n_vec < kMgCountLimit ? n_vec : kMgCountLimit;
-  if (rows == 0) return 0;
-  if (cols > kMgCountLimit / rows) return kMgCountLimit * real_bytes;
-  return rows * cols * real_bytes;
-}
-
-static int mg_sizes_multi(const char *name, int real_bytes, int64_t n_a, int64_t n_b, int64_t n_vec) {
-  const int st = mg_sizes(name, real_bytes, n_a, n_b);
-  if (st != TFEM_OK) return st;
-  if (n_vec < 1) return fail(TFEM_ERR_INVALID_ARGUMENT, "%s: n_vec must be at least 1", name);
-  return TFEM_OK;
-}
-
-// The row shape of a launch: n_vec if it is 2, 4 or 8 and every block is aligned to the access
-// width, else 0 (the generic instance).
-static int mg_row_width(int64_t n_vec, int real_bytes, std::initializer_list<const void *> blocks) {
-  if (n_vec != 2 && n_vec != 4 && n_vec != 8) return 0;
-  const uintptr_t width = uintptr_t(n_vec * real_bytes < 16 ? n_vec * real_bytes : 16);
-  for (const void *p : blocks)
-    if (reinterpret_cast<uintptr_t>(p) % width != 0) return 0;
-  return int(n_vec);
 }
 
 }  // namespace tfem

@@ -21,8 +21,8 @@ its sweep, the restriction of its residual to the level below and the prolongati
 h-level (``_Level``) runs them on single vectors (csrc/tfem_mg.hip) or on (n_l, k) blocks of
 right-hand sides (csrc/tfem_mg_multi.hip: ``vcycle_multi``, ``solve_multi``).  ``P2Multigrid`` puts
 a P2 level (``_P2Level``) on the finest mesh of such a hierarchy: P1 is a subspace of P2 on one
-mesh, the two transfers of that step are csrc/tfem_mg_p2.hip, and below it the same cycle goes on
-through the P1 levels.
+mesh, the two transfers of that step are csrc/tfem_mg_p2.hip (csrc/tfem_mg_p2_multi.hip on blocks),
+and below it the same cycle goes on through the P1 levels.
 """
 
 from __future__ import annotations
@@ -178,8 +178,9 @@ class _Level:
 
 class _P2Level(_Level):
     """The P2 space on the mesh of the P1 level below it.  P is the identity on the vertex DoFs and
-    0.5 / 0.5 on an edge DoF (the P2 numbering is "vertices, then edges"); the two transfers handle
-    one vector (there are no block forms of them), the sweep is the P1 levels'.
+    0.5 / 0.5 on an edge DoF (the P2 numbering is "vertices, then edges"); the two transfers are its
+    own, on one vector (csrc/tfem_mg_p2.hip) or on a block (csrc/tfem_mg_p2_multi.hip), the sweep is
+    the P1 levels'.
 
     A matrix-free P2 operator is applied in the ENGINE's numbering (the engine renumbers the edge
     DoFs of a basis from 50,000 DoFs on; the vertex ids stay those of the P1 level): the level is
@@ -212,16 +213,25 @@ class _P2Level(_Level):
 
     def restrict_residual(self, buffers, coarser, k, stream):
         (_, ax, r), (_, _, coarse_r) = buffers, coarser
-        status = self.lib.tfem_mg_p2_restrict_residual(
-            _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(self.coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
-            _ptr(coarse_r), self.real_bytes, self.n_v, self.n, stream)
+        if k is None:
+            status = self.lib.tfem_mg_p2_restrict_residual(
+                _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(self.coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
+                _ptr(coarse_r), self.real_bytes, self.n_v, self.n, stream)
+        else:
+            status = self.lib.tfem_mg_p2_restrict_residual_multi(
+                _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(self.coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
+                _ptr(coarse_r), self.real_bytes, self.n_v, self.n, k, stream)
         if status:
             _native.check(status)
 
     def prolong_add(self, buffers, coarser, k, stream):
         (x, _, _), (coarse_x, _, _) = buffers, coarser
-        status = self.lib.tfem_mg_p2_prolong_add(_ptr(self.edge_vertices), _ptr(self.mask), _ptr(coarse_x), _ptr(x),
-                                                 self.real_bytes, self.n_v, self.n, stream)
+        if k is None:
+            status = self.lib.tfem_mg_p2_prolong_add(_ptr(self.edge_vertices), _ptr(self.mask), _ptr(coarse_x),
+                                                     _ptr(x), self.real_bytes, self.n_v, self.n, stream)
+        else:
+            status = self.lib.tfem_mg_p2_prolong_add_multi(_ptr(self.edge_vertices), _ptr(self.mask), _ptr(coarse_x),
+                                                           _ptr(x), self.real_bytes, self.n_v, self.n, k, stream)
         if status:
             _native.check(status)
 
@@ -258,13 +268,20 @@ def _build_level(name, kind, mesh, element, bilinear, layouts):
 
 class _Hierarchy:
     """What ``GeometricMultigrid`` and ``P2Multigrid`` share: the preparation of a level's vectors,
-    its apply, THE cycle, and ``vcycle`` / ``solve`` on one vector.  A subclass sets ``levels``
-    (coarsest first), ``nu``, ``omega``, ``dirichlet``, ``device``, ``dtype``, ``_buffers`` (per level
-    the single-vector (x, ax, r)), ``_own`` (the levels whose applies it prepares itself) and
-    ``_applies`` (stream -> the prepared applies of ``_own``)."""
+    its apply, THE cycle, ``vcycle`` / ``solve`` on one vector and ``vcycle_multi`` / ``solve_multi``
+    on a block.  A subclass sets ``levels`` (coarsest first), ``nu``, ``omega``, ``dirichlet``,
+    ``device``, ``dtype``, ``_buffers`` (per level the single-vector (x, ax, r)), ``_own`` (the levels
+    whose applies and block buffers it keeps itself), ``_applies`` (stream -> the prepared applies of
+    ``_own``) and ``_blocks`` (k -> the block buffers of ``_own``; insertion order = age of last
+    use)."""
 
     #: how the refusal of a block (N, k) where one vector is expected ends
     _BLOCKS = "blocks: vcycle_multi, solve_multi"
+
+    #: ``vcycle_multi`` keeps the block buffers (x, K x, r per level, (n_l, k) each) of this many
+    #: widths k, the most recently used ones; an older width is dropped with the prepared launches
+    #: that point into its buffers and allocated again when it comes back.
+    BLOCK_WIDTHS_KEPT = 2
 
     # ------------------------------------------------------------------ set-up
     def _prepare_level(self, level, inward):
@@ -382,6 +399,152 @@ class _Hierarchy:
                                     rtol, maxiter)
         return self._result(x, b), it, res
 
+    # ------------------------------------------------------------------ blocks of right-hand sides
+    def _blocks_below(self, k):
+        """Per level below ``_own`` the (x, ax, r) of shape (n_l, k): those of the hierarchy that owns
+        these levels."""
+        return []
+
+    def _block_buffers(self, k):
+        """Per level (x, ax, r) of shape (n_l, k), zero on first use of the width k and reused; the
+        ``BLOCK_WIDTHS_KEPT`` most recently used widths are kept.  ``_blocks[k]`` holds those of
+        ``_own`` and, behind them, the direction and its image of ``solve_multi``."""
+        below = self._blocks_below(k)
+        buffers = self._blocks.pop(k, None)
+        if buffers is None:
+            buffers = [tuple(torch.zeros(level.n, k, dtype=self.dtype, device=self.device) for _ in range(3))
+                       for level in self._own]
+            # behind the levels: the direction and its image of solve_multi, allocated by its first use
+            buffers.append(None)
+            if len(self._blocks) >= self.BLOCK_WIDTHS_KEPT:
+                self._blocks.pop(next(iter(self._blocks)))
+                # the prepared launches keep the buffers they point into: drop them with the width
+                # (those of the widths that stay are prepared again on their next use)
+                self._applies = {}
+        self._blocks[k] = buffers  # the youngest
+        return below + buffers[:-1]
+
+    def _direction_buffers(self, k):
+        """The direction of ``solve_multi`` and its image, (N, k) each, kept with the width k (a
+        prepared launch keeps its two buffers); after ``_block_buffers(k)``."""
+        kept = self._blocks[k]
+        if kept[-1] is None:
+            n = self.levels[-1].n
+            kept[-1] = tuple(torch.empty(n, k, dtype=self.dtype, device=self.device) for _ in range(2))
+        return kept[-1]
+
+    def _block(self, V, what):
+        """``V`` (N, k) in the hierarchy's type and in the numbering of the finest level."""
+        top = self.levels[-1]
+        if V.dim() != 2 or V.shape[0] != top.n or V.shape[1] < 1:
+            raise ValueError(f"{type(self).__name__}.{what}: a block of shape ({top.n}, k) with k >= 1, "
+                             f"got {tuple(V.shape)}")
+        block = V.detach().to(self.device, self.dtype)
+        return top.engine._dofs_in(block) if top.crossing else block
+
+    def _block_result(self, X):
+        top = self.levels[-1]
+        if top.crossing:
+            X = top.engine._dofs_out(X)
+        return top.engine._home(X)
+
+    def _vcycle_multi_into(self, R):
+        """The cycle on the block buffers of R's width, R in the finest level's numbering; returns the
+        buffer that holds the result (valid until the next block cycle of that width)."""
+        k = int(R.shape[1])
+        buffers = self._block_buffers(k)
+        top = len(self.levels) - 1
+        buffers[top][2].copy_(R)
+        self._cycle(top, buffers, k, self._level_applies(), _native.current_stream(self.device))
+        return buffers[top][0]
+
+    def vcycle_multi(self, R):
+        """One V-cycle on every column of ``R`` (N, k), k >= 1: Z (N, k) with column j the approximate
+        solution of K z = r_j on the free DoFs, 0 on the held ones.  The cycle of ``vcycle``, every
+        launch on (n_l, k) row-major blocks: the block applies of the levels, the block kernels of
+        csrc/tfem_mg_multi.hip (on a P2 level the transfers of csrc/tfem_mg_p2_multi.hip), and one
+        dense product on the coarsest level.  The block buffers are separate from those of
+        ``vcycle`` and kept for the ``BLOCK_WIDTHS_KEPT`` most recently used widths."""
+        block = self._block(R, "vcycle_multi")
+        with torch.cuda.device(self.device):
+            Z = self._vcycle_multi_into(block).clone()
+        return self._block_result(Z)
+
+    def solve_multi(self, B, X0=None, rtol=1e-10, maxiter=100):
+        """``solve`` for the k columns of ``B`` (N, k) at once: k conjugate-gradient recurrences
+        preconditioned by ``vcycle_multi`` carried through one loop -- per iteration one block apply,
+        one block cycle, column-wise dot products, one alpha and one beta per column, and one host
+        read of the k relative residuals |r_j| / |m b_j|.  The contract of
+        ``conjugate_gradients_multi``: a column whose residual is <= rtol at a check is frozen from
+        then on -- its alpha and beta are 0 and its direction is zeroed, so its x and r stop
+        changing and no 0/0 arises (a column that starts converged, e.g. an all-zero one, takes no
+        iteration) -- and the loop ends when every column is frozen or after ``maxiter`` iterations.
+        The held DoFs keep X0's values (0 by default).  Returns (X (N, k), iterations (k,) int64,
+        relative residuals (k,)), the last two on the host; iterations[j] is the iteration at which
+        column j was frozen."""
+        name, top = type(self).__name__, self.levels[-1]
+        if B.dim() != 2 or B.shape[0] != top.n:
+            raise ValueError(f"{name}.solve_multi: B must have shape ({top.n}, k), got {tuple(B.shape)}")
+        rhs = self._block(B, "solve_multi")
+        n, k = rhs.shape
+        with torch.cuda.device(self.device):
+            # the blocks an apply is launched on are the kept ones of the width (a prepared launch
+            # keeps its two buffers): x and K x of the finest level, the direction and its image
+            buffers = self._block_buffers(k)
+            P, AP = self._direction_buffers(k)
+            apply = self._level_applies()[-1]
+            mask = None if top.mask is None else top.mask.reshape(n, 1)
+            if X0 is None:
+                X = torch.zeros(n, k, dtype=self.dtype, device=self.device)
+            else:
+                if tuple(X0.shape) != (n, k):
+                    raise ValueError(f"{name}.solve_multi: X0 must have B's shape ({n}, {k})")
+                X = self._block(X0, "solve_multi").clone(memory_format=torch.contiguous_format)
+            if X0 is None:
+                R = rhs.clone(memory_format=torch.contiguous_format)
+            else:
+                top_x, top_ax, _ = buffers[len(self.levels) - 1]
+                top_x.copy_(X)
+                apply(top_x, top_ax)
+                R = rhs - top_ax
+            if mask is not None:
+                R *= mask
+            b_norm = torch.linalg.vector_norm(rhs if mask is None else mask * rhs, dim=0).clamp_min(
+                torch.finfo(self.dtype).tiny)
+            res = torch.linalg.vector_norm(R, dim=0) / b_norm
+            active = res > rtol  # (k,) on the device; its host copy decides the loop
+            running = active.cpu()
+            its = torch.zeros(k, dtype=torch.int64, device="cpu")
+            it = 0
+            if maxiter > 0 and bool(running.any()):
+                one, zero = torch.ones((), dtype=self.dtype, device=self.device), torch.zeros(k, dtype=self.dtype,
+                                                                                              device=self.device)
+                P.copy_(self._vcycle_multi_into(R))
+                rz = (R * P).sum(0)
+                P.mul_(active)
+                while True:
+                    apply(P, AP)
+                    if mask is not None:
+                        AP *= mask
+                    pap = (P * AP).sum(0)
+                    alpha = torch.where(active, rz / torch.where(active, pap, one), zero)
+                    X.add_(alpha * P)
+                    R.sub_(alpha * AP)
+                    it += 1
+                    res_new = torch.linalg.vector_norm(R, dim=0) / b_norm
+                    res = torch.where(active, res_new, res)  # a frozen column reports what froze it
+                    its[running] = it
+                    active = active & (res > rtol)
+                    running = active.cpu()  # the host read of the iteration
+                    if it >= maxiter or not bool(running.any()):
+                        break
+                    Z = self._vcycle_multi_into(R)
+                    rz_new = (R * Z).sum(0)
+                    beta = torch.where(active, rz_new / torch.where(active, rz, one), zero)
+                    P.mul_(beta).add_(Z * active)
+                    rz = torch.where(active, rz_new, rz)
+        return self._block_result(X), its, res.cpu()
+
 
 class GeometricMultigrid(_Hierarchy):
     """V(nu, nu)-cycle and multigrid-preconditioned CG for a P1 form on ``levels`` uniform
@@ -407,11 +570,6 @@ class GeometricMultigrid(_Hierarchy):
     Refused with NotImplementedError: P2 elements (``P2Multigrid``), fracture bases, coefficient data
     (``basis.coefficient``: its shape belongs to one mesh), a custom set of free DoFs; and a coarse
     mesh with more than ``Basis.DENSE_SOLVE_LIMIT`` free DoFs."""
-
-    #: ``vcycle_multi`` keeps the block buffers (x, K x, r per level, (n_l, k) each) of this many
-    #: widths k, the most recently used ones; an older width is dropped with the prepared launches
-    #: that point into its buffers and allocated again when it comes back.
-    BLOCK_WIDTHS_KEPT = 2
 
     def __init__(self, coarse_triangulation, levels, bilinear, quadrature_order=2, dirichlet=True, nu=2,
                  omega=2.0 / 3.0, dtype=None, *, element=None):
@@ -490,128 +648,6 @@ class GeometricMultigrid(_Hierarchy):
             else:
                 level.inverse[level.free[:, None], level.free[None, :]] = inverse
 
-    # ------------------------------------------------------------------ blocks of right-hand sides
-    def _block_buffers(self, k):
-        """Per level (x, ax, r) of shape (n_l, k), zero on first use of the width k and reused; the
-        ``BLOCK_WIDTHS_KEPT`` most recently used widths are kept."""
-        buffers = self._blocks.pop(k, None)
-        if buffers is None:
-            buffers = [tuple(torch.zeros(level.n, k, dtype=self.dtype, device=self.device) for _ in range(3))
-                       for level in self.levels]
-            # behind the levels: the direction and its image of solve_multi, allocated by its first use
-            buffers.append(None)
-            if len(self._blocks) >= self.BLOCK_WIDTHS_KEPT:
-                self._blocks.pop(next(iter(self._blocks)))
-                # the prepared launches keep the buffers they point into: drop them with the width
-                # (those of the widths that stay are prepared again on their next use)
-                self._applies = {}
-        self._blocks[k] = buffers  # the youngest
-        return buffers
-
-    def _block(self, V, what):
-        if V.dim() != 2 or V.shape[0] != self.levels[-1].n or V.shape[1] < 1:
-            raise ValueError(f"GeometricMultigrid.{what}: a block of shape ({self.levels[-1].n}, k) with k >= 1, "
-                             f"got {tuple(V.shape)}")
-        return V.detach().to(self.device, self.dtype)
-
-    def _vcycle_multi_into(self, R):
-        """The cycle on the block buffers of R's width; returns the buffer that holds the result
-        (valid until the next block cycle of that width)."""
-        k = int(R.shape[1])
-        buffers = self._block_buffers(k)
-        top = len(self.levels) - 1
-        buffers[top][2].copy_(R)
-        self._cycle(top, buffers, k, self._level_applies(), _native.current_stream(self.device))
-        return buffers[top][0]
-
-    def vcycle_multi(self, R):
-        """One V-cycle on every column of ``R`` (N, k), k >= 1: Z (N, k) with column j the approximate
-        solution of K z = r_j on the free DoFs, 0 on the held ones.  The cycle of ``vcycle``, every
-        launch on (n_l, k) row-major blocks: the block applies of the levels, the block kernels of
-        csrc/tfem_mg_multi.hip, and one dense product on the coarsest level.  The block buffers are separate from those of
-        ``vcycle`` and kept for the ``BLOCK_WIDTHS_KEPT`` most recently used widths."""
-        block = self._block(R, "vcycle_multi")
-        with torch.cuda.device(self.device):
-            Z = self._vcycle_multi_into(block).clone()
-        return self.levels[-1].engine._home(Z)
-
-    def solve_multi(self, B, X0=None, rtol=1e-10, maxiter=100):
-        """``solve`` for the k columns of ``B`` (N, k) at once: k conjugate-gradient recurrences
-        preconditioned by ``vcycle_multi`` carried through one loop -- per iteration one block apply,
-        one block cycle, column-wise dot products, one alpha and one beta per column, and one host
-        read of the k relative residuals |r_j| / |m b_j|.  The contract of
-        ``conjugate_gradients_multi``: a column whose residual is <= rtol at a check is frozen from
-        then on -- its alpha and beta are 0 and its direction is zeroed, so its x and r stop
-        changing and no 0/0 arises (a column that starts converged, e.g. an all-zero one, takes no
-        iteration) -- and the loop ends when every column is frozen or after ``maxiter`` iterations.
-        The held DoFs keep X0's values (0 by default).  Returns (X (N, k), iterations (k,) int64,
-        relative residuals (k,)), the last two on the host; iterations[j] is the iteration at which
-        column j was frozen."""
-        top = self.levels[-1]
-        if B.dim() != 2 or B.shape[0] != top.n:
-            raise ValueError(f"GeometricMultigrid.solve_multi: B must have shape ({top.n}, k), got {tuple(B.shape)}")
-        rhs = self._block(B, "solve_multi")
-        n, k = rhs.shape
-        with torch.cuda.device(self.device):
-            # the blocks an apply is launched on are the kept ones of the width (a prepared launch
-            # keeps its two buffers): x and K x of the finest level, the direction and its image
-            buffers = self._block_buffers(k)
-            if buffers[-1] is None:
-                buffers[-1] = tuple(torch.empty(n, k, dtype=self.dtype, device=self.device) for _ in range(2))
-            P, AP = buffers[-1]
-            apply = self._level_applies()[-1]
-            mask = None if top.mask is None else top.mask.reshape(n, 1)
-            if X0 is None:
-                X = torch.zeros(n, k, dtype=self.dtype, device=self.device)
-            else:
-                if tuple(X0.shape) != (n, k):
-                    raise ValueError(f"GeometricMultigrid.solve_multi: X0 must have B's shape ({n}, {k})")
-                X = X0.detach().to(self.device, self.dtype).clone(memory_format=torch.contiguous_format)
-            if X0 is None:
-                R = rhs.clone(memory_format=torch.contiguous_format)
-            else:
-                top_x, top_ax, _ = buffers[len(self.levels) - 1]
-                top_x.copy_(X)
-                apply(top_x, top_ax)
-                R = rhs - top_ax
-            if mask is not None:
-                R *= mask
-            b_norm = torch.linalg.vector_norm(rhs if mask is None else mask * rhs, dim=0).clamp_min(
-                torch.finfo(self.dtype).tiny)
-            res = torch.linalg.vector_norm(R, dim=0) / b_norm
-            active = res > rtol  # (k,) on the device; its host copy decides the loop
-            running = active.cpu()
-            its = torch.zeros(k, dtype=torch.int64, device="cpu")
-            it = 0
-            if maxiter > 0 and bool(running.any()):
-                one, zero = torch.ones((), dtype=self.dtype, device=self.device), torch.zeros(k, dtype=self.dtype,
-                                                                                              device=self.device)
-                P.copy_(self._vcycle_multi_into(R))
-                rz = (R * P).sum(0)
-                P.mul_(active)
-                while True:
-                    apply(P, AP)
-                    if mask is not None:
-                        AP *= mask
-                    pap = (P * AP).sum(0)
-                    alpha = torch.where(active, rz / torch.where(active, pap, one), zero)
-                    X.add_(alpha * P)
-                    R.sub_(alpha * AP)
-                    it += 1
-                    res_new = torch.linalg.vector_norm(R, dim=0) / b_norm
-                    res = torch.where(active, res_new, res)  # a frozen column reports what froze it
-                    its[running] = it
-                    active = active & (res > rtol)
-                    running = active.cpu()  # the host read of the iteration
-                    if it >= maxiter or not bool(running.any()):
-                        break
-                    Z = self._vcycle_multi_into(R)
-                    rz_new = (R * Z).sum(0)
-                    beta = torch.where(active, rz_new / torch.where(active, rz, one), zero)
-                    P.mul_(beta).add_(Z * active)
-                    rz = torch.where(active, rz_new, rz)
-        return top.engine._home(X), its, res.cpu()
-
     def __repr__(self):
         sizes = ", ".join(str(level.n) for level in self.levels)
         return (f"GeometricMultigrid({len(self.levels) - 1} refinements: {sizes} DoFs, V({self.nu},{self.nu}), "
@@ -637,13 +673,19 @@ class P2Multigrid(_Hierarchy):
 
     A matrix-free P2 operator is applied in the ENGINE's numbering (the engine renumbers the edge
     DoFs of a basis from 50,000 DoFs on; the vertex ids stay those of the P1 level): the tables,
-    masks and weights of the P2 level are built in that numbering and vectors cross once at the
-    boundary of ``vcycle`` / ``solve``.
+    masks and weights of the P2 level are built in that numbering and vectors and blocks cross once
+    at the boundary of ``vcycle`` / ``solve`` / ``vcycle_multi`` / ``solve_multi``.
 
-    Refused with NotImplementedError: what ``GeometricMultigrid`` refuses, blocks (N, k) of vectors
-    (``vcycle_multi`` / ``solve_multi`` are not built for P2) and a custom set of free DoFs."""
+    ``vcycle`` and ``solve`` take one vector.  Blocks (N, k) of right-hand sides go through
+    ``vcycle_multi`` and ``solve_multi``, with the contracts of ``GeometricMultigrid``'s: the P2 level
+    runs its sweeps, its block apply and its two transfers (csrc/tfem_mg_p2_multi.hip) on its own
+    (N, k) buffers, and below it the block cycle runs on the P1 hierarchy's block buffers of the same
+    width, so the number of launches does not depend on k.
 
-    _BLOCKS = "vcycle_multi and solve_multi are not built for P2"
+    Refused with NotImplementedError: what ``GeometricMultigrid`` refuses and a custom set of free
+    DoFs."""
+
+    _BLOCKS = "blocks: vcycle_multi, solve_multi of P2Multigrid"
 
     def __init__(self, coarse_triangulation, levels, bilinear, quadrature_order=3, dirichlet=True, nu=2,
                  omega=2.0 / 3.0, dtype=None):
@@ -667,9 +709,13 @@ class P2Multigrid(_Hierarchy):
         self._own = [top]
         self._buffers = self.p1._buffers + [(top.x, top.ax, top.r)]
         self._applies = {}  # stream -> the prepared apply of the P2 level
+        self._blocks = {}  # k -> (x, ax, r) of shape (N, k) of the P2 level; insertion order = age of last use
 
     def _level_applies(self):
         return self.p1._level_applies() + super()._level_applies()
+
+    def _blocks_below(self, k):
+        return self.p1._block_buffers(k)
 
     def __repr__(self):
         sizes = ", ".join(str(level.n) for level in self.levels)
