@@ -797,6 +797,42 @@ int tfem_cg_direction(void *p, const void *r, const void *inv_diag, const int32_
                       void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The same loop around a preconditioner that hands z = M^-1 r over as a VECTOR (the V-cycle of the
+ * multigrid hierarchies): per iteration
+ *   AP = K P (an apply), tfem_cg_dot, tfem_pcg_update, [the preconditioner: r -> z], tfem_pcg_rz,
+ *   tfem_pcg_direction
+ * Vectors, widths, `active`, `step` and the workspace are those of tfem_cg_* above (the workspace
+ * of tfem_cg_workspace_bytes with the same five buffers), and so are the reductions: per-workgroup
+ * partial sums, finished by every workgroup of a later launch in one fixed order.
+ *   mask (n reals) stands where inv_diag stands above: mask[i] == 0 marks a HELD DoF, any other
+ *        value a free one (no mask: a vector of ones).  A held row is never written by update /
+ *        direction and takes no part in any sum (it is skipped, not multiplied by 0: its ap and z
+ *        may be anything, NaN included).  tfem_cg_dot takes the mask as its inv_diag.
+ * start:     p = z on the rows that are not held, 0 on the held ones; partials of r.z into parity 1,
+ *            the one step 0 reads as "previous".
+ * update:    alpha_j = active[j] ? r.z_j(parity (step - 1) & 1) / p.Ap_j : 0; x += alpha p,
+ *            r -= alpha ap on the rows that are not held of the active columns; partials of r.r
+ *            (every column, the frozen ones included) into parity step & 1.  Writes no r.z.
+ * rz:        partials of r.z over the rows that are not held into parity step & 1.
+ * direction: beta_j = r.z_j(step & 1) / r.z_j((step - 1) & 1); p = z + beta p on the rows that are
+ *            not held of the active columns; nothing of a frozen column is written.
+ * One launch each; no allocation, no synchronisation.  The refusals are those of tfem_cg_*:
+ * TFEM_ERR_INVALID_ARGUMENT for real_bytes not 4 or 8, a negative size or step, a NULL array with
+ * n > 0 and n_vec > 0; TFEM_ERR_INDEX_RANGE for a vector of 4 GiB or more.  Nothing is launched
+ * after a refusal; n == 0 or n_vec == 0 succeeds and launches nothing.
+ * ------------------------------------------------------------------------- */
+int tfem_pcg_start(const void *r, const void *z, const void *mask, void *p, int real_bytes,
+                   int64_t n, int64_t n_vec, void *ws, void *stream);
+int tfem_pcg_update(void *x, void *r, const void *p, const void *ap, const void *mask,
+                    const int32_t *active, int real_bytes, int64_t n, int64_t n_vec, int64_t step,
+                    void *ws, void *stream);
+int tfem_pcg_rz(const void *r, const void *z, const void *mask, int real_bytes, int64_t n,
+                int64_t n_vec, int64_t step, void *ws, void *stream);
+int tfem_pcg_direction(void *p, const void *z, const void *mask, const int32_t *active,
+                       int real_bytes, int64_t n, int64_t n_vec, int64_t step, const void *ws,
+                       void *stream);
+
+/* ------------------------------------------------------------------------- *
  * The vector part of a geometric multigrid V-cycle on nested P1 spaces (a mesh and its red
  * refinement; the reference has no multigrid, this stands where its dense solve stops being
  * possible, abstract_basis.py:114-117,177-195).  All arrays DEVICE; vectors of reals of real_bytes

@@ -170,6 +170,18 @@ SIGNATURES = {
     "tfem_cg_direction": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p],
     ),
+    "tfem_pcg_start": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p],
+    ),
+    "tfem_pcg_update": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p,
+         c_void_p],
+    ),
+    "tfem_pcg_rz": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "tfem_pcg_direction": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p],
+    ),
     "tfem_mg_smooth": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "tfem_mg_restrict_residual": (
         c_int,

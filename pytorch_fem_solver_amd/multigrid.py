@@ -23,6 +23,10 @@ right-hand sides (csrc/tfem_mg_multi.hip: ``vcycle_multi``, ``solve_multi``).  `
 a P2 level (``_P2Level``) on the finest mesh of such a hierarchy: P1 is a subspace of P2 on one
 mesh, the two transfers of that step are csrc/tfem_mg_p2.hip (csrc/tfem_mg_p2_multi.hip on blocks),
 and below it the same cycle goes on through the P1 levels.
+
+The conjugate-gradient recurrence around the cycle runs on the device as well (``_fused_cycle_pcg``
+over csrc/tfem_pcg.hip, the default of ``solve`` / ``solve_multi`` on a HIP device); ``_cycle_pcg``
+and the body of ``solve_multi`` are the same recurrence in torch operations (``loop="torch"``).
 """
 
 from __future__ import annotations
@@ -36,7 +40,7 @@ from . import _native, meshgen
 from .basis import Basis, forms
 from .element import ElementTri
 from .mesh import MeshTri
-from .sparse import FormOperator, _into, _is_block
+from .sparse import FormOperator, _cg_loop, _into, _is_block
 
 __all__ = ["GeometricMultigrid", "P2Multigrid"]
 
@@ -104,6 +108,123 @@ def _cycle_pcg(apply, cycle, mask, rhs, x0, rtol, maxiter):
             p.mul_(rz_new / rz).add_(z)
             rz = rz_new
     return x, it, res
+
+
+#: how the fused loop reads |r|^2 every iteration: "drain" is one blocking copy after the update;
+#: "overlap" copies it asynchronously into pinned memory and waits only after the next cycle, rz,
+#: direction, apply and dot have been enqueued.  None: by the width of the block.  On an MI355X
+#: (profiles/mg_fused.log, 986,049 DoFs) the overlapped read saves 0.5 - 1.8 ms of a 10 - 15 ms
+#: solve on one and two columns, where the queue runs empty while the host decides; at four
+#: columns the two are level and at eight the draining read is 1 % ahead on the P2 hierarchy,
+#: because the launches are then long enough to keep the queue filled either way.
+_PCG_READ = None
+_PCG_OVERLAP_WIDTHS = 2  # the widest block that reads overlapped
+
+
+def _fused_cycle_pcg(lib, apply, cycle, mask, rhs, R, Z, P, AP, x0, rtol, maxiter):
+    """The recurrences of ``_cycle_pcg`` (rhs of shape (n,)) and of ``solve_multi`` (rhs of shape
+    (n, k)) with the vector part in libtfem_hip (csrc/tfem_pcg.hip).  ``R`` is the residual buffer
+    the cycle reads and ``Z`` the buffer it leaves z in (``cycle()`` takes no argument and copies
+    nothing), ``P`` and ``AP`` the kept direction and its image, all shaped like rhs; ``mask`` is the
+    (n,) vector whose zeros mark the held DoFs (None: none is held).  Per iteration: ``apply(P,
+    AP)``, tfem_cg_dot, tfem_pcg_update, the check, ``cycle()``, tfem_pcg_rz, tfem_pcg_direction --
+    alpha, beta and the dot products stay on the device, and the only torch operations are the sum
+    of the G partial sums of |r_j|^2 and its copy to the host (in the form ``_PCG_READ`` names; the
+    overlapped form has run one cycle, rz, direction, apply and dot more than it needed when the
+    check ends the loop before ``maxiter``; they write neither x nor r).
+    Returns (X shaped like rhs, iterations (k,) int64, relative residuals (k,) float64), the last
+    two on the host."""
+    from .sparse import cg_workspace
+
+    read = _PCG_READ
+    if read not in (None, "drain", "overlap"):
+        raise ValueError(f"_PCG_READ must be None, 'drain' or 'overlap', not {read!r}")
+    n = rhs.shape[0]
+    k = 1 if rhs.dim() == 1 else rhs.shape[1]
+    if read is None:
+        read = "overlap" if k <= _PCG_OVERLAP_WIDTHS else "drain"
+    device, dtype = rhs.device, rhs.dtype
+    as_block = lambda t: t.view(n, k)  # noqa: E731
+    if x0 is None:
+        X = torch.zeros_like(R)
+        R.copy_(rhs)
+    else:
+        X = x0.clone(memory_format=torch.contiguous_format)
+        P.copy_(X)
+        apply(P, AP)
+        torch.sub(rhs, AP, out=R)
+    if mask is None:
+        b_norm = torch.linalg.vector_norm(as_block(rhs), dim=0)
+        mask = torch.ones(n, dtype=dtype, device=device)  # the launches take a mask: nothing is held
+    else:
+        as_block(R).mul_(mask.view(n, 1))
+        b_norm = torch.linalg.vector_norm(as_block(rhs) * mask.view(n, 1), dim=0)
+    b_norm = b_norm.clamp_min(torch.finfo(dtype).tiny)
+    res = (torch.linalg.vector_norm(as_block(R), dim=0) / b_norm).double().cpu()
+    b_norm = b_norm.double().cpu()
+    running = res > rtol  # (k,) on the host: it decides the loop
+    its = torch.zeros(k, dtype=torch.int64, device="cpu")
+    if n == 0 or maxiter <= 0 or not bool(running.any()):
+        return X, its, res
+    ws = cg_workspace(n, k, device)
+    flags_host = running.to(torch.int32)
+    flags = flags_host.to(device)
+    stream = _native.current_stream(device)
+    size = (rhs.element_size(), n, k)
+    x_, r_, z_, p_, ap_, m_, f_, w_ = (_ptr(t) for t in (X, R, Z, P, AP, mask, flags, ws))
+    dot, update, rz, direction = lib.tfem_cg_dot, lib.tfem_pcg_update, lib.tfem_pcg_rz, lib.tfem_pcg_direction
+    dot_args = (p_, ap_, m_, *size, w_, stream)
+    cycle()
+    _native.check(lib.tfem_pcg_start(r_, z_, m_, p_, *size, w_, stream))
+    if not bool(running.all()):
+        as_block(P).mul_(flags)  # once: the direction of a column that starts converged is zero
+    rr_partials = (ws[2], ws[4])  # the r.r buffers of the two parities
+    overlap = read == "overlap"
+    if overlap:
+        rr = torch.empty(k, dtype=torch.float64, device=device)
+        rr_host = torch.empty(k, dtype=torch.float64, device="cpu").pin_memory()
+        flags_host = flags_host.pin_memory()
+        arrived = torch.cuda.Event()
+    apply(P, AP)
+    status = dot(*dot_args)
+    it = 0
+    while True:
+        status = status or update(x_, r_, p_, ap_, m_, f_, *size, it, w_, stream)
+        if status:
+            _native.check(status)
+        partials = rr_partials[it & 1]  # (G, k): |r_j|^2 after this update
+        if overlap:
+            torch.sum(partials, dim=0, out=rr)
+            rr_host.copy_(rr, non_blocking=True)
+            arrived.record()
+            if it + 1 < maxiter:  # ahead of the decision: none of these writes x or r
+                cycle()
+                status = (rz(r_, z_, m_, *size, it, w_, stream) or direction(p_, z_, m_, f_, *size, it, w_, stream))
+                apply(P, AP)
+                status = status or dot(*dot_args)
+            arrived.synchronize()
+            rr_now = rr_host
+        else:
+            rr_now = partials.sum(0).cpu()  # the host read of the iteration
+        it += 1
+        res = torch.where(running, rr_now.sqrt() / b_norm, res)  # a frozen column reports what froze it
+        its[running] = it
+        still = running & (res > rtol)
+        if it >= maxiter or not bool(still.any()):
+            break
+        if not bool((still == running).all()):
+            running = still
+            flags_host.copy_(running)
+            flags.copy_(flags_host, non_blocking=True)  # before the next update: the column's x and r stay
+        if not overlap:
+            cycle()
+            status = (rz(r_, z_, m_, *size, it - 1, w_, stream)
+                      or direction(p_, z_, m_, f_, *size, it - 1, w_, stream))
+            apply(P, AP)
+            status = status or dot(*dot_args)
+    if status:
+        _native.check(status)
+    return X, its, res
 
 
 class _Level:
@@ -283,6 +404,9 @@ class _Hierarchy:
     #: that point into its buffers and allocated again when it comes back.
     BLOCK_WIDTHS_KEPT = 2
 
+    #: the direction and its image of the fused loop of ``solve``, allocated by its first use
+    _directions = None
+
     # ------------------------------------------------------------------ set-up
     def _prepare_level(self, level, inward):
         """Mask, smoothing weights and buffers of ``level`` in the numbering it runs in; ``inward``
@@ -385,18 +509,41 @@ class _Hierarchy:
             z = self._vcycle_into(flat).clone()
         return self._result(z, r)
 
-    def solve(self, b, x0=None, rtol=1e-10, maxiter=100, free=None):
+    def _fused_pcg(self, rhs, start, k, rtol, maxiter):
+        """``_fused_cycle_pcg`` on the hierarchy's own buffers: the vectors of the levels (k None) or
+        their blocks of width k.  The residual lives in the top level's r buffer and z is read from
+        its x buffer, so nothing is copied into the cycle or out of it."""
+        top = len(self.levels) - 1
+        buffers = self._buffers if k is None else self._block_buffers(k)
+        P, AP = self._direction_buffers(k)
+        applies, stream = self._level_applies(), _native.current_stream(self.device)
+        Z, _, R = buffers[top]
+        return _fused_cycle_pcg(self.levels[top].lib, applies[-1],
+                                lambda: self._cycle(top, buffers, k, applies, stream), self.levels[top].mask, rhs,
+                                R, Z, P, AP, start, rtol, maxiter)
+
+    def solve(self, b, x0=None, rtol=1e-10, maxiter=100, free=None, loop=None):
         """Conjugate gradients preconditioned by ``vcycle`` for K x = b on the free DoFs (the held
         ones keep x0's values, 0 by default).  The relative residual |r| / |m b| is checked every
-        iteration.  Returns (x shaped like b, iterations, relative residual)."""
+        iteration.  Returns (x shaped like b, iterations, relative residual).
+
+        ``loop``: "fused" keeps the recurrence on the device (csrc/tfem_pcg.hip: four vector launches
+        per iteration around the apply and the cycle, alpha, beta and the dot products never leave
+        the device, one host read of |r|^2 per iteration); "torch" is the loop of torch operations;
+        None is the fused loop for a ``b`` on a HIP device unless TFEM_CG=torch (``sparse._cg_loop``)."""
         if free is not None:
             raise NotImplementedError(f"{type(self).__name__}.solve: a custom set of free DoFs; the hierarchy holds "
                                       "the boundary DoFs of every level (dirichlet=True) or none")
+        loop = _cg_loop(loop, b.device)
         rhs = self._vector(b, "solve")
         start = None if x0 is None else self._vector(x0, "solve")
         with torch.cuda.device(self.device):
-            x, it, res = _cycle_pcg(self._level_applies()[-1], self._vcycle_into, self.levels[-1].mask, rhs, start,
-                                    rtol, maxiter)
+            if loop == "fused":
+                x, its, ress = self._fused_pcg(rhs, start, None, rtol, maxiter)
+                it, res = int(its[0]), float(ress[0])
+            else:
+                x, it, res = _cycle_pcg(self._level_applies()[-1], self._vcycle_into, self.levels[-1].mask, rhs,
+                                        start, rtol, maxiter)
         return self._result(x, b), it, res
 
     # ------------------------------------------------------------------ blocks of right-hand sides
@@ -426,7 +573,13 @@ class _Hierarchy:
 
     def _direction_buffers(self, k):
         """The direction of ``solve_multi`` and its image, (N, k) each, kept with the width k (a
-        prepared launch keeps its two buffers); after ``_block_buffers(k)``."""
+        prepared launch keeps its two buffers); after ``_block_buffers(k)``.  k None: the two vectors
+        (N,) of the fused loop of ``solve``."""
+        if k is None:
+            if self._directions is None:
+                n = self.levels[-1].n
+                self._directions = tuple(torch.empty(n, dtype=self.dtype, device=self.device) for _ in range(2))
+            return self._directions
         kept = self._blocks[k]
         if kept[-1] is None:
             n = self.levels[-1].n
@@ -470,7 +623,7 @@ class _Hierarchy:
             Z = self._vcycle_multi_into(block).clone()
         return self._block_result(Z)
 
-    def solve_multi(self, B, X0=None, rtol=1e-10, maxiter=100):
+    def solve_multi(self, B, X0=None, rtol=1e-10, maxiter=100, loop=None):
         """``solve`` for the k columns of ``B`` (N, k) at once: k conjugate-gradient recurrences
         preconditioned by ``vcycle_multi`` carried through one loop -- per iteration one block apply,
         one block cycle, column-wise dot products, one alpha and one beta per column, and one host
@@ -481,12 +634,27 @@ class _Hierarchy:
         iteration) -- and the loop ends when every column is frozen or after ``maxiter`` iterations.
         The held DoFs keep X0's values (0 by default).  Returns (X (N, k), iterations (k,) int64,
         relative residuals (k,)), the last two on the host; iterations[j] is the iteration at which
-        column j was frozen."""
+        column j was frozen.
+
+        ``loop`` as in ``solve``.  The fused loop (csrc/tfem_pcg.hip) carries the k recurrences in the
+        same four launches per iteration whatever k is; a frozen column's x and r are never written
+        again (its direction is no longer updated instead of being zeroed), and the residuals come
+        back in float64."""
         name, top = type(self).__name__, self.levels[-1]
         if B.dim() != 2 or B.shape[0] != top.n:
             raise ValueError(f"{name}.solve_multi: B must have shape ({top.n}, k), got {tuple(B.shape)}")
+        loop = _cg_loop(loop, B.device)
         rhs = self._block(B, "solve_multi")
         n, k = rhs.shape
+        if loop == "fused":
+            start = None
+            if X0 is not None:
+                if tuple(X0.shape) != (n, k):
+                    raise ValueError(f"{name}.solve_multi: X0 must have B's shape ({n}, {k})")
+                start = self._block(X0, "solve_multi")
+            with torch.cuda.device(self.device):
+                X, its, res = self._fused_pcg(rhs, start, k, rtol, maxiter)
+            return self._block_result(X), its, res
         with torch.cuda.device(self.device):
             # the blocks an apply is launched on are the kept ones of the width (a prepared launch
             # keeps its two buffers): x and K x of the finest level, the direction and its image
