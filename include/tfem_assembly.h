@@ -864,7 +864,7 @@ int tfem_mg_restrict_residual(const int32_t *ptr, const int32_t *idx, const void
 int tfem_mg_prolong_add(const int32_t *parents, const void *mask_f, const void *e_c, void *x_f,
                         int real_bytes, int64_t n_f, int64_t n_c, void *stream);
 
-/* The same three on a block of n_vec >= 1 vectors (csrc/tfem_mg_multi.hip).  x, b, ax, b_f, ax_f,
+/* The same three on a block of n_vec >= 1 vectors (csrc/tfem_mg.hip).  x, b, ax, b_f, ax_f,
  * r_c, e_c, x_f are n x n_vec reals, ROW-major: the n_vec values of a DoF are consecutive (the
  * layout of tfem_p1_apply_rings_multi, tfem_csr_spmm and tfem_cg_*); w, the masks, ptr, idx and
  * parents keep one entry per DoF.  One launch for any n_vec; n_vec == 1 IS the single launch above.
@@ -892,7 +892,7 @@ int tfem_mg_restrict_residual_multi(const int32_t *ptr, const int32_t *idx, cons
 int tfem_mg_prolong_add_multi(const int32_t *parents, const void *mask_f, const void *e_c, void *x_f,
                               int real_bytes, int64_t n_f, int64_t n_c, int64_t n_vec, void *stream);
 
-/* The transfers between the P2 space and the P1 space of ONE mesh (csrc/tfem_mg_p2.hip): the step
+/* The transfers between the P2 space and the P1 space of ONE mesh (csrc/tfem_mg.hip): the step
  * from a P2 level down to the P1 hierarchy above.  The P2 level has n_f = n_v + n_e DoFs, vertices
  * first, then edges; edge DoF n_v + j has the endpoints edge_vertices[2 j], edge_vertices[2 j + 1]
  * (n_e x 2 int32, vertex ids in either order).  P is the identity on the vertex rows and 0.5 / 0.5
@@ -918,7 +918,7 @@ int tfem_mg_p2_restrict_residual(const int32_t *ptr, const int32_t *idx, const v
 int tfem_mg_p2_prolong_add(const int32_t *edge_vertices, const void *mask_f, const void *e_c, void *x_f,
                            int real_bytes, int64_t n_v, int64_t n_f, void *stream);
 
-/* The same two on a block of n_vec >= 1 vectors (csrc/tfem_mg_p2_multi.hip).  b_f, ax_f, r_c, e_c,
+/* The same two on a block of n_vec >= 1 vectors (csrc/tfem_mg.hip).  b_f, ax_f, r_c, e_c,
  * x_f are n x n_vec reals, ROW-major (the layout of tfem_mg_*_multi and tfem_p2_apply_rows_multi);
  * the masks, ptr, idx and edge_vertices keep one entry per DoF.  One launch for any n_vec;
  * n_vec == 1 IS the single launch above.

@@ -18,11 +18,11 @@ operator (the post-smoothing is the adjoint of the pre-smoothing), so it may pre
 The cycle is written once (``_Hierarchy._cycle``) over a list of levels, a list of their (x, K x, r)
 buffers and a list of their applies.  A level makes the three vector launches of libtfem_hip itself:
 its sweep, the restriction of its residual to the level below and the prolongation from there.  An
-h-level (``_Level``) runs them on single vectors (csrc/tfem_mg.hip) or on (n_l, k) blocks of
-right-hand sides (csrc/tfem_mg_multi.hip: ``vcycle_multi``, ``solve_multi``).  ``P2Multigrid`` puts
-a P2 level (``_P2Level``) on the finest mesh of such a hierarchy: P1 is a subspace of P2 on one
-mesh, the two transfers of that step are csrc/tfem_mg_p2.hip (csrc/tfem_mg_p2_multi.hip on blocks),
-and below it the same cycle goes on through the P1 levels.
+h-level (``_Level``) runs them on single vectors or on (n_l, k) blocks of right-hand sides
+(``vcycle_multi``, ``solve_multi``); all of them are csrc/tfem_mg.hip.  ``P2Multigrid`` puts a P2
+level (``_P2Level``) on the finest mesh of such a hierarchy: P1 is a subspace of P2 on one mesh, the
+two transfers of that step are the other transfer kind of the same kernels (``tfem_mg_p2_*``), and
+below it the same cycle goes on through the P1 levels.
 
 The conjugate-gradient recurrence around the cycle runs on the device as well (``_fused_cycle_pcg``
 over csrc/tfem_pcg.hip, the default of ``solve`` / ``solve_multi`` on a HIP device); ``_cycle_pcg``
@@ -254,43 +254,36 @@ class _Level:
         self.pt_ptr = torch.as_tensor(ptr, device=device)
         self.pt_idx = torch.as_tensor(idx, device=device)
 
+    def _launch(self, name, k, head, tail):
+        """The entry point ``name`` on vectors (``k`` None) or ``name + "_multi"`` on (n_l, k) blocks,
+        whose arguments are the single ones with n_vec = k between ``head`` and ``tail``."""
+        if k is None:
+            status = getattr(self.lib, name)(*head, *tail)
+        else:
+            status = getattr(self.lib, name + "_multi")(*head, k, *tail)
+        if status:
+            _native.check(status)
+
     def smooth(self, buffers, k, first, stream):
         """x = w r (``first``) or x += w (r - K x)."""
         x, ax, r = buffers
-        if k is None:
-            status = self.lib.tfem_mg_smooth(_ptr(x), _ptr(r), None if first else _ptr(ax), _ptr(self.w),
-                                             self.real_bytes, self.n, 1 if first else 0, stream)
-        else:
-            status = self.lib.tfem_mg_smooth_multi(_ptr(x), _ptr(r), None if first else _ptr(ax), _ptr(self.w),
-                                                   self.real_bytes, self.n, k, 1 if first else 0, stream)
-        if status:
-            _native.check(status)
+        self._launch("tfem_mg_smooth", k,
+                     (_ptr(x), _ptr(r), None if first else _ptr(ax), _ptr(self.w), self.real_bytes, self.n),
+                     (1 if first else 0, stream))
 
     def restrict_residual(self, buffers, coarser, k, stream):
         """r of the level below = m_c P^T( m (r - K x) )."""
         coarse, (_, ax, r), (_, _, coarse_r) = self.coarse, buffers, coarser
-        if k is None:
-            status = self.lib.tfem_mg_restrict_residual(
-                _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
-                _ptr(coarse_r), self.real_bytes, coarse.n, self.n, stream)
-        else:
-            status = self.lib.tfem_mg_restrict_residual_multi(
-                _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
-                _ptr(coarse_r), self.real_bytes, coarse.n, self.n, k, stream)
-        if status:
-            _native.check(status)
+        self._launch("tfem_mg_restrict_residual", k,
+                     (_ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
+                      _ptr(coarse_r), self.real_bytes, coarse.n, self.n), (stream,))
 
     def prolong_add(self, buffers, coarser, k, stream):
         """x += m P (x of the level below)."""
         coarse, (x, _, _), (coarse_x, _, _) = self.coarse, buffers, coarser
-        if k is None:
-            status = self.lib.tfem_mg_prolong_add(_ptr(self.parents), _ptr(self.mask), _ptr(coarse_x), _ptr(x),
-                                                  self.real_bytes, self.n, coarse.n, stream)
-        else:
-            status = self.lib.tfem_mg_prolong_add_multi(_ptr(self.parents), _ptr(self.mask), _ptr(coarse_x), _ptr(x),
-                                                        self.real_bytes, self.n, coarse.n, k, stream)
-        if status:
-            _native.check(status)
+        self._launch("tfem_mg_prolong_add", k,
+                     (_ptr(self.parents), _ptr(self.mask), _ptr(coarse_x), _ptr(x), self.real_bytes, self.n, coarse.n),
+                     (stream,))
 
     def __repr__(self):
         extra = ", renumbered by the engine" if self.engine.renumbered else ""
@@ -300,8 +293,8 @@ class _Level:
 class _P2Level(_Level):
     """The P2 space on the mesh of the P1 level below it.  P is the identity on the vertex DoFs and
     0.5 / 0.5 on an edge DoF (the P2 numbering is "vertices, then edges"); the two transfers are its
-    own, on one vector (csrc/tfem_mg_p2.hip) or on a block (csrc/tfem_mg_p2_multi.hip), the sweep is
-    the P1 levels'.
+    own (``tfem_mg_p2_*``, the P2 kind of the transfers of csrc/tfem_mg.hip) on one vector or on a
+    block, the sweep is the P1 levels'.
 
     A matrix-free P2 operator is applied in the ENGINE's numbering (the engine renumbers the edge
     DoFs of a basis from 50,000 DoFs on; the vertex ids stay those of the P1 level): the level is
@@ -334,27 +327,15 @@ class _P2Level(_Level):
 
     def restrict_residual(self, buffers, coarser, k, stream):
         (_, ax, r), (_, _, coarse_r) = buffers, coarser
-        if k is None:
-            status = self.lib.tfem_mg_p2_restrict_residual(
-                _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(self.coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
-                _ptr(coarse_r), self.real_bytes, self.n_v, self.n, stream)
-        else:
-            status = self.lib.tfem_mg_p2_restrict_residual_multi(
-                _ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(self.coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
-                _ptr(coarse_r), self.real_bytes, self.n_v, self.n, k, stream)
-        if status:
-            _native.check(status)
+        self._launch("tfem_mg_p2_restrict_residual", k,
+                     (_ptr(self.pt_ptr), _ptr(self.pt_idx), _ptr(self.coarse.mask), _ptr(self.mask), _ptr(r), _ptr(ax),
+                      _ptr(coarse_r), self.real_bytes, self.n_v, self.n), (stream,))
 
     def prolong_add(self, buffers, coarser, k, stream):
         (x, _, _), (coarse_x, _, _) = buffers, coarser
-        if k is None:
-            status = self.lib.tfem_mg_p2_prolong_add(_ptr(self.edge_vertices), _ptr(self.mask), _ptr(coarse_x),
-                                                     _ptr(x), self.real_bytes, self.n_v, self.n, stream)
-        else:
-            status = self.lib.tfem_mg_p2_prolong_add_multi(_ptr(self.edge_vertices), _ptr(self.mask), _ptr(coarse_x),
-                                                           _ptr(x), self.real_bytes, self.n_v, self.n, k, stream)
-        if status:
-            _native.check(status)
+        self._launch("tfem_mg_p2_prolong_add", k,
+                     (_ptr(self.edge_vertices), _ptr(self.mask), _ptr(coarse_x), _ptr(x), self.real_bytes, self.n_v,
+                      self.n), (stream,))
 
 
 def _build_level(name, kind, mesh, element, bilinear, layouts):
@@ -614,9 +595,9 @@ class _Hierarchy:
     def vcycle_multi(self, R):
         """One V-cycle on every column of ``R`` (N, k), k >= 1: Z (N, k) with column j the approximate
         solution of K z = r_j on the free DoFs, 0 on the held ones.  The cycle of ``vcycle``, every
-        launch on (n_l, k) row-major blocks: the block applies of the levels, the block kernels of
-        csrc/tfem_mg_multi.hip (on a P2 level the transfers of csrc/tfem_mg_p2_multi.hip), and one
-        dense product on the coarsest level.  The block buffers are separate from those of
+        launch on (n_l, k) row-major blocks: the block applies of the levels, the block forms of the
+        kernels of csrc/tfem_mg.hip (on a P2 level the P2 kind of its transfers), and one dense
+        product on the coarsest level.  The block buffers are separate from those of
         ``vcycle`` and kept for the ``BLOCK_WIDTHS_KEPT`` most recently used widths."""
         block = self._block(R, "vcycle_multi")
         with torch.cuda.device(self.device):
@@ -830,7 +811,7 @@ class P2Multigrid(_Hierarchy):
     the P1 operator of the finest mesh IS the Galerkin operator P^T K2 P of the P2 one: no triple
     product here either.  The cycle is the one of ``GeometricMultigrid`` run over ``levels``, the P1
     levels and then the P2 level: the P2 level sweeps with w = omega * m2 / diag K2 and makes its own
-    two transfers (csrc/tfem_mg_p2.hip), and below it the cycle runs on the P1 hierarchy's own
+    two transfers (``tfem_mg_p2_*``, csrc/tfem_mg.hip), and below it the cycle runs on the P1 hierarchy's own
     buffers with the P1 hierarchy's own prepared applies.
 
     The arguments are those of ``GeometricMultigrid`` (``levels`` refinements below the mesh that
@@ -846,7 +827,7 @@ class P2Multigrid(_Hierarchy):
 
     ``vcycle`` and ``solve`` take one vector.  Blocks (N, k) of right-hand sides go through
     ``vcycle_multi`` and ``solve_multi``, with the contracts of ``GeometricMultigrid``'s: the P2 level
-    runs its sweeps, its block apply and its two transfers (csrc/tfem_mg_p2_multi.hip) on its own
+    runs its sweeps, its block apply and its two transfers (``tfem_mg_p2_*_multi``) on its own
     (N, k) buffers, and below it the block cycle runs on the P1 hierarchy's block buffers of the same
     width, so the number of launches does not depend on k.
 

@@ -167,6 +167,65 @@ def test_prolong_kernel(mesh, masked, dtype, np_dtype):
     _close(runs[0], want, scale, 2, np_dtype, f"prolong {mesh} masked={masked}")
 
 
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("dtype,np_dtype", DTYPES)
+def test_entries_outside_the_arrays_read_zero_and_write_nothing(masked, dtype, np_dtype):
+    """An idx entry >= n_f and a parent >= n_c count as 0 -- just behind the array, where memory
+    holds other numbers, and at 2^32 / real_bytes + 3, where a 32-bit byte offset would wrap into
+    the array again; the outputs end where they are said to end (canaries behind r_c and x_f).  The
+    bounds are those of test_restrict_kernel and test_prolong_kernel."""
+    n_c, n_f, parents, ptr, idx = _tables("square5")
+    wrap = (1 << 32) // np.dtype(np_dtype).itemsize + 3
+    assert wrap < 2**31
+    rng = np.random.default_rng(14)
+    pad = 64
+    b, a = _random(rng, n_f + pad, np_dtype), _random(rng, n_f + pad, np_dtype)  # numbers behind the arrays
+    m_c = _random(rng, n_c, np_dtype, mask=True) if masked else None
+    m_f = np.ones(n_f + pad, dtype=np_dtype)
+    m_f[:n_f] = _random(rng, n_f, np_dtype, mask=True)
+    m_f[3] = 1  # the entry a wrapped offset would read
+    dev = lambda v, n: None if v is None else torch.tensor(v)[:n]  # noqa: E731
+    outside = np.array([2, 9, 17, 40])
+    bad_idx = idx.copy()
+    bad_idx[outside] = [n_f, n_f + 5, wrap, wrap]
+    out = torch.full((n_c + pad,), 7.0, dtype=dtype)
+    _call("tfem_mg_restrict_residual", torch.tensor(ptr), torch.tensor(bad_idx), dev(m_c, n_c),
+          dev(m_f, n_f) if masked else None, dev(b, n_f), dev(a, n_f), out[:n_c], out.element_size(), n_c, n_f)
+    got = out.cpu().numpy()
+    assert (got[n_c:] == 7.0).all(), "the kernel wrote behind r_c"
+    rows = np.repeat(np.arange(n_c), np.diff(ptr))
+    weight = m_f[:n_f].astype(LD) if masked else np.ones(n_f, dtype=LD)
+    terms = 0.5 * weight[idx] * (b.astype(LD)[idx] - a.astype(LD)[idx])
+    sizes = 0.5 * weight[idx] * (np.abs(b.astype(LD))[idx] + np.abs(a.astype(LD))[idx])
+    assert (np.abs(b[3] - a[3]) > 0) and (sizes[outside] > 0).any()
+    terms[outside], sizes[outside] = 0, 0
+    want, scale = np.zeros(n_c, dtype=LD), np.zeros(n_c, dtype=LD)
+    np.add.at(want, rows, terms)
+    np.add.at(scale, rows, sizes)
+    if masked:
+        want, scale = m_c * want, m_c * scale
+    _close(got[:n_c], want, scale, 16, np_dtype, f"restrict with entries outside masked={masked}")
+
+    e = _random(rng, n_c + pad, np_dtype)
+    bad_parents = parents.copy()
+    bad_parents[30] = (n_c, parents[30, 1])  # one parent just behind e_c
+    bad_parents[41] = (n_c + 7, wrap)  # both outside
+    bad_parents[52] = (parents[52, 0], wrap)
+    x = _random(rng, n_f + pad, np_dtype)
+    xd = torch.tensor(x)
+    _call("tfem_mg_prolong_add", torch.tensor(bad_parents), dev(m_f, n_f) if masked else None, dev(e, n_c), xd[:n_f],
+          xd.element_size(), n_f, n_c)
+    got = xd.cpu().numpy()
+    assert (got[n_f:] == x[n_f:]).all(), "the kernel wrote behind x_f"
+    assert got[41] == x[41], "a vertex with both parents outside adds 0"
+    el = np.concatenate([e[:n_c], np.zeros(1, dtype=np_dtype)]).astype(LD)
+    ends = np.where(bad_parents.astype(np.int64) >= n_c, n_c, bad_parents.astype(np.int64))
+    ea, eb = el[ends[:, 0]], el[ends[:, 1]]
+    want = x[:n_f].astype(LD) + weight * 0.5 * (ea + eb)
+    scale = np.abs(x[:n_f].astype(LD)) + weight * 0.5 * (np.abs(ea) + np.abs(eb))
+    _close(got[:n_f], want, scale, 2, np_dtype, f"prolong with parents outside masked={masked}")
+
+
 # --------------------------------------------------------------------------------- the cycle
 _MODELS, _SOLVERS = {}, {}
 

@@ -1,5 +1,5 @@
 """Geometric multigrid on blocks of right-hand sides, on a real MI355X: the three tfem_mg_*_multi
-kernels (csrc/tfem_mg_multi.hip) bit for bit against the single kernels on every column and against
+kernels (csrc/tfem_mg.hip) bit for bit against the single kernels on every column and against
 numpy in extended precision, ``GeometricMultigrid.vcycle_multi`` against the CPU model of
 tests/multigrid_reference.py on every column, and ``solve_multi`` against the model's PCG with
 columns that freeze at different times.  Tables, hierarchies, models and solvers are those of

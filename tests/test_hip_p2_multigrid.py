@@ -1,4 +1,4 @@
-"""P2 multigrid on a real MI355X: the two tfem_mg_p2_* kernels (csrc/tfem_mg_p2.hip) against numpy
+"""P2 multigrid on a real MI355X: the two tfem_mg_p2_* kernels (csrc/tfem_mg.hip) against numpy
 in extended precision, the V-cycle of P2Multigrid against the CPU model of
 tests/p2_multigrid_reference.py on every route of the P2 operator (matrix-free in the caller's
 numbering, matrix-free in the engine's edge numbering, assembled CSR), and the

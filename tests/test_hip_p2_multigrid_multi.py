@@ -1,5 +1,5 @@
 """P2 multigrid on blocks of right-hand sides, on a real MI355X: the two tfem_mg_p2_*_multi kernels
-(csrc/tfem_mg_p2_multi.hip) bit for bit against the single kernels on every column and against numpy
+(csrc/tfem_mg.hip) bit for bit against the single kernels on every column and against numpy
 in extended precision, ``P2Multigrid.vcycle_multi`` against the CPU model of
 tests/p2_multigrid_reference.py on every column and on every route of the P2 operator, the sequence
 of its launches, and ``solve_multi`` against the model's PCG with columns that freeze at different

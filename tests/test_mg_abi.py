@@ -1,6 +1,7 @@
 """The tfem_mg_* entry points (csrc/tfem_mg.hip) as far as a machine without a GPU can tell: the
 declarations, the exports, the refusals decided on the host before any launch, and the register
-report of the kernels (no instance may use scratch memory)."""
+report of every kernel of the file, the block forms and the P2 transfers included (no instance may
+use scratch memory or more than 64 VGPRs)."""
 
 import ctypes
 import os
@@ -119,25 +120,41 @@ def test_mg_launches_refuse_bad_arguments_without_a_device():
     assert lib.tfem_mg_prolong_add(None, None, None, None, 8, 0, 7, None) == 0
 
 
-def test_no_mg_kernel_uses_scratch_memory(tmp_path):
-    """Every instance of csrc/tfem_mg.hip, compiled for gfx950 with the build's own flags: no
-    scratch memory (tools/kernel_regs.py on the assembly).  Smooth: two types x aligned or not x
-    first or not; restrict and prolong: two types."""
+# kernel name pattern -> instances.  smooth, single and block: two types x aligned or not x first or
+# not; restrict and prolong: two types x two kinds x the row shapes 1, 2, 4, 8, and two types x two
+# kinds of the instance for any width
+INSTANCES = (("k_mg_smooth<", 8), ("k_mg_smooth_multi<", 8), ("k_mg_restrict<", 16), ("k_mg_restrict_any<", 4),
+             ("k_mg_prolong<", 16), ("k_mg_prolong_any<", 4))
+
+
+def test_all_56_mg_kernels_use_no_scratch_memory_and_at_most_64_vgprs(tmp_path):
+    """Every instance of csrc/tfem_mg.hip -- the sweeps and the transfers of both kinds, on single
+    vectors and on blocks --, compiled for gfx950 with the build's own flags (tools/kernel_regs.py on
+    the assembly): the documented 56 instances, none with scratch memory, LDS or more than 64 VGPRs."""
     import __graft_entry__ as entry
 
     name = "tfem_mg.hip"
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.exists(hipcc):
         pytest.fail(f"{hipcc} not found: the kernels cannot be compiled")
+    source = open(os.path.join(entry.CSRC, name)).read()
+    assert "56 in all" in source, "the file documents the number of its instances"
     flags = [f for f in entry.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + entry.PER_FILE_FLAGS.get(name, [])
     asm = tmp_path / "mg.s"
     subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", "-I" + os.path.join(REPO, "include"),
                     "-o", str(asm), os.path.join(entry.CSRC, name)], check=True, capture_output=True)
-    for kernel, instances in (("k_mg_smooth", 8), ("k_mg_restrict", 2), ("k_mg_prolong", 2)):
+    line = r"vgpr\s+(\d+) sgpr\s+(\d+) scratch\s+(\d+) lds\s+(\d+)\s+(.*)"
+    total = 0
+    for kernel, instances in INSTANCES:
         out = subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_regs.py"), str(asm), kernel],
                              check=True, capture_output=True, text=True).stdout
-        rows = [re.match(r"vgpr\s+(\d+) sgpr\s+(\d+) scratch\s+(\d+) lds\s+(\d+)\s+(.*)", line) for line in out.splitlines()]
+        print(out)
+        rows = [re.match(line, text) for text in out.splitlines()]
         assert rows and all(rows), out[-2000:]
-        bad = [m.group(5) for m in rows if int(m.group(3)) != 0 or int(m.group(1)) > 64]
+        bad = [m.group(5) for m in rows if int(m.group(3)) != 0 or int(m.group(1)) > 64 or int(m.group(4)) != 0]
         assert not bad, bad
         assert len(rows) == instances, out
+        total += len(rows)
+    everything = subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_regs.py"), str(asm)],
+                                check=True, capture_output=True, text=True).stdout
+    assert len(everything.splitlines()) == total == 56, everything

@@ -1,15 +1,12 @@
-"""The tfem_mg_p2_* entry points (csrc/tfem_mg_p2.hip) as far as a machine without a GPU can tell:
-the declarations, the exports, the refusals decided on the host before any launch, and the register
-report of the kernels (no instance may use scratch memory)."""
+"""The tfem_mg_p2_* entry points (csrc/tfem_mg.hip, the P2 kind of its transfers) as far as a machine
+without a GPU can tell: the declarations, the exports and the refusals decided on the host before
+any launch.  The register report of their kernels is in tests/test_mg_abi.py."""
 
 import ctypes
 import os
 import re
 import shutil
 import subprocess
-import sys
-
-import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -114,28 +111,3 @@ def test_p2_launches_refuse_bad_arguments_without_a_device():
     assert lib.tfem_mg_p2_restrict_residual(None, None, None, None, None, None, None, 4, 0, 7, None) == 0
     assert lib.tfem_mg_p2_prolong_add(None, None, None, None, 8, 0, 7, None) == 0
     assert lib.tfem_mg_p2_prolong_add(None, None, None, None, 8, 0, 0, None) == 0
-
-
-def test_no_p2_transfer_kernel_uses_scratch_memory(tmp_path):
-    """Every instance of csrc/tfem_mg_p2.hip, compiled for gfx950 with the build's own flags: no
-    scratch memory and at most 64 vector registers (tools/kernel_regs.py on the assembly); two types
-    per kernel."""
-    import __graft_entry__ as entry
-
-    name = "tfem_mg_p2.hip"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.fail(f"{hipcc} not found: the kernels cannot be compiled")
-    flags = [f for f in entry.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + entry.PER_FILE_FLAGS.get(name, [])
-    asm = tmp_path / "mg_p2.s"
-    subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", "-I" + os.path.join(REPO, "include"),
-                    "-o", str(asm), os.path.join(entry.CSRC, name)], check=True, capture_output=True)
-    for kernel, instances in (("k_mg_p2_restrict", 2), ("k_mg_p2_prolong", 2)):
-        out = subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_regs.py"), str(asm), kernel],
-                             check=True, capture_output=True, text=True).stdout
-        print(out)
-        rows = [re.match(r"vgpr\s+(\d+) sgpr\s+(\d+) scratch\s+(\d+) lds\s+(\d+)\s+(.*)", line) for line in out.splitlines()]
-        assert rows and all(rows), out[-2000:]
-        bad = [m.group(5) for m in rows if int(m.group(3)) != 0 or int(m.group(1)) > 64]
-        assert not bad, bad
-        assert len(rows) == instances, out

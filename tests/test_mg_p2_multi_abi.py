@@ -1,16 +1,13 @@
-"""The tfem_mg_p2_*_multi entry points (csrc/tfem_mg_p2_multi.hip) as far as a machine without a GPU
-can tell, after tests/test_mg_p2_abi.py and tests/test_mg_multi_abi.py: the declarations, the
-exports, the refusals decided on the host before any launch, and the register report of the kernels
-(no scratch, at most 64 VGPRs, the documented number of instances)."""
+"""The tfem_mg_p2_*_multi entry points (csrc/tfem_mg.hip, the P2 kind of its transfers) as far as a
+machine without a GPU can tell, after tests/test_mg_p2_abi.py and tests/test_mg_multi_abi.py: the
+declarations, the exports and the refusals decided on the host before any launch.  The register
+report of their kernels is in tests/test_mg_abi.py."""
 
 import ctypes
 import os
 import re
 import shutil
 import subprocess
-import sys
-
-import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -132,42 +129,3 @@ def test_p2_multi_launches_refuse_bad_arguments_without_a_device():
     # n_vec = 1 IS the single launch: its refusals carry the single entry point's name
     assert lib.tfem_mg_p2_prolong_add_multi(a[0], a[1], a[2], a[2], 8, 10, 30, 1, None) == INVALID
     assert b"tfem_mg_p2_prolong_add:" in lib.tfem_last_error()
-
-
-# kernel name pattern -> instances, as the head of the file documents them: two types x the row
-# shapes 2, 4, 8, and two types of the instance for any width
-INSTANCES = (("k_mg_p2_restrict_multi<", 6), ("k_mg_p2_restrict_multi_any<", 2),
-             ("k_mg_p2_prolong_multi<", 6), ("k_mg_p2_prolong_multi_any<", 2))
-
-
-def test_no_p2_multi_kernel_uses_scratch_memory_or_more_than_64_vgprs(tmp_path):
-    """Every instance of csrc/tfem_mg_p2_multi.hip, compiled for gfx950 with the build's own flags
-    (tools/kernel_regs.py on the assembly): 16 instances, none with scratch memory or more than 64
-    VGPRs, the bound of tfem_mg_multi.hip and tfem_mg_p2.hip."""
-    import __graft_entry__ as entry
-
-    name = "tfem_mg_p2_multi.hip"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.fail(f"{hipcc} not found: the kernels cannot be compiled")
-    source = open(os.path.join(entry.CSRC, name)).read()
-    assert "16 in all" in source, "the file documents the number of its instances"
-    flags = [f for f in entry.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + entry.PER_FILE_FLAGS.get(name, [])
-    asm = tmp_path / "mg_p2_multi.s"
-    subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", "-I" + os.path.join(REPO, "include"),
-                    "-o", str(asm), os.path.join(entry.CSRC, name)], check=True, capture_output=True)
-    line = r"vgpr\s+(\d+) sgpr\s+(\d+) scratch\s+(\d+) lds\s+(\d+)\s+(.*)"
-    total = 0
-    for kernel, instances in INSTANCES:
-        out = subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_regs.py"), str(asm), kernel],
-                             check=True, capture_output=True, text=True).stdout
-        print(out)
-        rows = [re.match(line, text) for text in out.splitlines()]
-        assert rows and all(rows), out[-2000:]
-        bad = [m.group(5) for m in rows if int(m.group(3)) != 0 or int(m.group(1)) > 64 or int(m.group(4)) != 0]
-        assert not bad, bad
-        assert len(rows) == instances, out
-        total += len(rows)
-    everything = subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_regs.py"), str(asm)],
-                                check=True, capture_output=True, text=True).stdout
-    assert len(everything.splitlines()) == total == 16, everything
